@@ -2,6 +2,7 @@
 """LED-Net hot-path benchmark (driver contract: see the round prompt).
 
   python bench.py --gpus N --steps K --warmup W [--mode train|infer] [--dtype bf16|f32]
+                  [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one synthetic batch already resident
 in HBM: mode=train -> forward + OHEM-CE loss + backward + SGD on 16 x 3 x 1024 x 1024
@@ -10,11 +11,18 @@ fusion + argmax on 8 x 3 x 1024 x 1024 per GPU (configs[1]).  N>1 is launched by
 torch.distributed.run, one rank per GPU (RCCL); images are sharded across ranks
 (weak scaling), value = images of all ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line with the contract fields plus
-  "roofline":     dominant kernel's achieved rate vs the gfx950 peak, timed with
-                  HIP events on the launch stream inside the timed region;
+A plain run sets up, warms up, times K steps and prints ONE JSON line (rank 0) with
+the contract fields.  --dump-outputs DIR writes what a step of the timed path computed
+(rank 0) as DIR/<name>.npy: the last timed step for inference; for training one more
+step from the run's start state (the timed steps' state diverges from run to run, see
+main()).  --full adds the measurements that take runs of their own:
+  "roofline":     per-kernel rates vs the gfx950 peaks, timed with HIP events in an
+                  instrumented eager pass of the same step after the timed region
+                  (with the launch and collective counts of `config`);
+  "deterministic_mode": the step re-captured in deterministic mode and timed;
   "cpu_baseline": the CPU oracle (oracle/spec.py, stock PyTorch fp32 ops) timed on
-                  this box's host cores on a bounded sample of the same workload.
+                  this box's host cores on a bounded sample of the same workload;
+  "parity":       bf16 flip rate against that oracle at the bench image size.
 """
 import argparse
 import json
@@ -228,18 +236,63 @@ def _coll_launches(log):
     return n
 
 
+DUMP_BUDGET_BYTES = 63 * 10 ** 6     # all arrays of one dump together (plus .npy headers) stay under 64 MB
+
+
+def step_outputs(mode, result, model):
+    """name -> tensor: what a caller of the timed step receives.  train: the loss dict of the step and the
+    parameters and floating-point buffers (BatchNorm running statistics) it updated, each flattened in
+    named_parameters() / named_buffers() order; infer: the fused logits and the argmax mask."""
+    if mode == 'train':
+        arrays = {k: v.detach() for k, v in result.items()}
+        arrays['parameters'] = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters()])
+        arrays['buffers'] = torch.cat([b.detach().reshape(-1).float() for _, b in model.named_buffers()
+                                       if b.is_floating_point()])
+        return arrays
+    logits, mask = result
+    return {'seg_logits': logits, 'pred_sem_seg': mask}
+
+
+def dump_outputs(arrays, out_dir, seed=304):
+    """DIR/<name>.npy in float32 (float64 stays float64).  When the whole set exceeds DUMP_BUDGET_BYTES, every
+    array larger than its equal share of the budget is replaced by a fixed sample of its flattened elements: the
+    sorted first indices of a permutation drawn from `seed` (the same positions in every run of the same command)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    dtype = {k: torch.float64 if v.dtype == torch.float64 else torch.float32 for k, v in arrays.items()}
+    size = {k: v.numel() * (8 if dtype[k] == torch.float64 else 4) for k, v in arrays.items()}
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    whole = sum(size.values()) <= DUMP_BUDGET_BYTES
+    for k, v in arrays.items():
+        t = v.detach().to(dtype[k])
+        note = f'{tuple(v.shape)}'
+        if not whole and size[k] > share:
+            n = share // t.element_size()
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(seed))[:n].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+            note += f', sample of {n} of {v.numel()} elements (seed {seed})'
+        np.save(os.path.join(out_dir, f'{k}.npy'), t.cpu().numpy())
+        print(f'[bench] dump-outputs: {k}.npy {note}', file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=None, help='ranks (one per GPU); default: WORLD_SIZE when launched by torch.distributed.run, else 1')
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps (at least 1)')
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the instrumented eager pass (roofline, launch and collective '
+                         'counts), the deterministic-mode probe, the CPU-oracle baseline and the bf16 parity check')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what a step of the timed path computed (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all; training: one more step from the run's start state")
     ap.add_argument('--mode', default=None, choices=['train', 'infer'])
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
     ap.add_argument('--batch', type=int, default=None)
     ap.add_argument('--height', type=int, default=1024)
     ap.add_argument('--width', type=int, default=1024)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-baseline-seconds', type=float, default=20.0, help='budget of the bounded CPU-oracle sample')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU-oracle baseline and parity legs')
+    ap.add_argument('--cpu-baseline-seconds', type=float, default=20.0, help='budget of the bounded CPU-oracle sample (--full)')
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
     ap.add_argument('--collectives', default=None, choices=['auto', 'rccl', 'torch'],
                     help='N>1: rccl = ncclAllReduce on the launch stream (graph-capturable), torch = torch.distributed (eager); '
@@ -250,10 +303,12 @@ def main():
     ap.add_argument('--deterministic', action='store_true',
                     help='run the whole bench in deterministic mode (LEDN_OPT_DETERMINISTIC: fixed-order reductions, no f32 atomics)')
     ap.add_argument('--no-det-probe', action='store_true',
-                    help='skip the deterministic-mode cost measurement after the timed region (profiling runs: keeps its kernels out of the rocprofv3 statistics)')
+                    help='--full without the deterministic-mode cost measurement after the timed region (profiling runs: keeps its kernels out of the rocprofv3 statistics)')
     ap.add_argument('--trace-only', action='store_true',
                     help='stop after the timed region (for rocprofv3 timeline traces: no instrumented eager pass, no JSON)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.gpus is None:
         args.gpus = int(os.environ.get('WORLD_SIZE', 1))
 
@@ -331,6 +386,9 @@ def main():
     if mode == 'train':
         trainer = L.Trainer(model, cfg, world_size=world, collectives=args.collectives)
         samples = [L.SegDataSample(gt=lab[i]) for i in range(bs)]
+        # --dump-outputs: the state every run starts from (weights, BatchNorm statistics, momentum, schedule position)
+        start = (({k: v.detach().clone() for k, v in model.state_dict().items()}, trainer.flat_mom.clone(), trainer.iter)
+                 if args.dump_outputs else None)
 
         def eager_step():
             return trainer.train_step(img, samples)
@@ -368,85 +426,60 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            result = step()
         barrier()
         dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        if mode == 'train':
+            # A training step sums gradients with float atomics, so its result differs from run to run in the last bits,
+            # and SGD on the one resident batch amplifies that over the capture, warm-up and timed steps (DESIGN.md
+            # section 8).  The dumped step is one more step of the timed path, taken from the run's start state: the
+            # same inputs and state in every run, outputs equal up to the rounding of one step.  (Every rank takes it:
+            # its collectives must stay matched.)
+            with Watchdog('dump step', 420):
+                with torch.no_grad():
+                    for k, v in model.state_dict().items():
+                        v.copy_(start[0][k])
+                    trainer.flat_mom.copy_(start[1])
+                trainer.iter = start[2]
+                result = step()
+                barrier()
+        if rank == 0:
+            # (graph replay of the inference pass returns nothing: its outputs live in the captured static tensors)
+            dump_outputs(step_outputs(mode, static_out if mode == 'infer' and graphed else result, model), args.dump_outputs)
     if args.trace_only:
         if rank == 0:
             print(f'[bench] trace-only: {bs * world * args.steps / dt:.1f} images/s', file=sys.stderr)
         if world > 1:
             dist.destroy_process_group()
         return
-    # per-kernel HIP-event timing needs individual launches and costs two event records per launch:
-    # an instrumented eager pass of the same step right after the timed region (every rank runs it,
-    # the collectives stay matched; rank 0 reports)
-    k_steps = min(args.steps, 5)
-    with Watchdog('instrumented eager pass', 420):
-        eager_step()
-        barrier()
-        ops.start_timing()
-        coll_log = None
-        if mode == 'train':
-            from led_net_amd import train as _TR
-            coll_log = _TR._Collective.log = []
-        try:
-            for _ in range(k_steps):
-                eager_step()
+    if args.full:
+        # per-kernel HIP-event timing needs individual launches and costs two event records per launch:
+        # an instrumented eager pass of the same step right after the timed region (every rank runs it,
+        # the collectives stay matched; rank 0 reports)
+        k_steps = min(args.steps, 5)
+        with Watchdog('instrumented eager pass', 420):
+            eager_step()
             barrier()
-        finally:
+            ops.start_timing()
+            coll_log = None
             if mode == 'train':
-                _TR._Collective.log = None
-        launches = ops.stop_timing()
+                from led_net_amd import train as _TR
+                coll_log = _TR._Collective.log = []
+            try:
+                for _ in range(k_steps):
+                    eager_step()
+                barrier()
+            finally:
+                if mode == 'train':
+                    _TR._Collective.log = None
+            launches = ops.stop_timing()
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
 
     if rank == 0:
-        # ---- dominant kernel FUNCTION (as rocprofv3 --stats groups them, template instances merged)
-        # by summed HIP-event time; its roofline = the larger of its two time floors
-        # (algorithmic bytes / HBM peak, algorithmic flops / dense MFMA peak)
-        agg, fam = {}, {}
-        for r in launches:
-            k = (r['entry'], r['sig'])
-            a = agg.setdefault(k, dict(ms=0.0, n=0, bytes=r['bytes'], flops=r['flops'], kernel=r['kernel']))
-            a['ms'] += r['ms']
-            a['n'] += 1
-            f = fam.setdefault(r['kernel'], dict(ms=0.0, n=0, bytes=0, flops=0))
-            f['ms'] += r['ms']
-            f['n'] += 1
-            f['bytes'] += r['bytes']
-            f['flops'] += r['flops']
-        top = sorted(agg.items(), key=lambda kv: -kv[1]['ms'])
-        kname, f = max(fam.items(), key=lambda kv: kv[1]['ms'])
-        avg_ms = f['ms'] / f['n']
-        gbs = f['bytes'] / (f['ms'] * 1e-3) / 1e9
-        tfl = f['flops'] / (f['ms'] * 1e-3) / 1e12
-        peak_t = MFMA_PEAK_TFLOPS[args.dtype]
-        mfma_bound = f['flops'] / (peak_t * 1e12) > f['bytes'] / (HBM_PEAK_GBS * 1e9)
-        if mfma_bound:
-            roof = dict(bound='mfma', achieved=round(tfl, 3), peak=peak_t, unit='TFLOP/s', frac=round(tfl / peak_t, 5))
-        else:
-            roof = dict(bound='hbm', achieved=round(gbs, 1), peak=HBM_PEAK_GBS, unit='GB/s',
-                        frac=round(gbs / HBM_PEAK_GBS, 5))
-        roof['traffic'] = pmc_traffic(kname, mode, args.dtype)
-        roof['mfma_busy'] = pmc_record(kname, mode, args.dtype).get('mfma_busy_frac')   # SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x kernel cycles), same PMC collection
-        roof.update(kernel=kname, avg_us=round(avg_ms * 1e3, 2), launches_per_step=f['n'] // k_steps,
-                    alg_bytes_per_launch=f['bytes'] // f['n'], alg_flops_per_launch=f['flops'] // f['n'],
-                    alg_gbs=round(gbs, 1), alg_tflops=round(tfl, 3), mfma_frac=round(tfl / peak_t, 5),
-                    arithmetic_intensity=round(f['flops'] / max(1, f['bytes']), 1),
-                    share_of_gpu_time=round(f['ms'] / max(1e-9, sum(v['ms'] for v in fam.values())), 4))
-        # the other kernel functions by time, each against the same two roofs (the convolution work is spread over five
-        # matrix-core kernels since round 3: the dominant one alone no longer describes it)
-        roof['by_kernel'] = []
-        for kn, ff in sorted(fam.items(), key=lambda kv: -kv[1]['ms'])[:8]:
-            g_, t_ = ff['bytes'] / (ff['ms'] * 1e-3) / 1e9, ff['flops'] / (ff['ms'] * 1e-3) / 1e12
-            roof['by_kernel'].append(dict(kernel=kn, ms_per_step=round(ff['ms'] / k_steps, 3), launches_per_step=ff['n'] // k_steps,
-                                          avg_us=round(ff['ms'] / ff['n'] * 1e3, 2), alg_gbs=round(g_, 1), hbm_frac=round(g_ / HBM_PEAK_GBS, 4),
-                                          alg_tflops=round(t_, 2), mfma_frac=round(t_ / peak_t, 4)))
-        total_flops = sum(v['flops'] * v['n'] for k, v in agg.items() if k[0] in ('ledn_conv2d', 'ledn_conv2d_wgrad', 'ledn_window_attn'))
-        total_bytes = sum(v['bytes'] * v['n'] for v in agg.values())
-        gpu_ms = sum(v['ms'] for v in agg.values())
         out = {
             'metric': 'images/sec at 1024x1024, LED-Net fwd+bwd' if mode == 'train'
                       else 'images/sec at 1024x1024, LED-Net fwd (inference)',
@@ -471,54 +504,100 @@ def main():
                        'collective_path': (None if mode != 'train' or trainer._all_reduce is None else
                                            ('one launch stream, one ordered collective sequence per rank (default for N > 1)'
                                             if trainer._single_stream else 'LEDN_EXPERIMENTAL=1 LEDN_MULTI_COMM=1: one communicator per branch stream')),
-                       'collectives_per_step': (None if not coll_log else
-                                                sum(1 for c in coll_log if c[1] == 'all_reduce') // k_steps),
-                       'collective_launches_per_step': (None if not coll_log else _coll_launches(coll_log) // k_steps),
-                       'collective_bytes_per_step': (None if not coll_log else
-                                                     4 * sum(c[2] for c in coll_log if c[1] == 'all_reduce') // k_steps),
-                       'kernel_launches_per_step': len(launches) // k_steps,
-                       'submission': 'hipGraph replay' if graphed else 'eager launches',
-                       'kernel_timing': 'HIP events on the launch streams, instrumented eager pass of the same step right after the timed region',
-                       'conv_gemm_tflops_whole_step': round(total_flops / (gpu_ms * 1e-3) / 1e12, 3),
-                       'hbm_alg_gbs_whole_step': round(total_bytes / (gpu_ms * 1e-3) / 1e9, 1),
-                       'gpu_busy_frac': round(gpu_ms / k_steps / (dt / args.steps * 1e3), 3)},
-            'roofline': roof,
+                       'submission': 'hipGraph replay' if graphed else 'eager launches'},
         }
         out['config']['deterministic'] = bool(L.is_deterministic())
-        if mode == 'train' and world == 1 and graphed and not L.is_deterministic() and not args.no_det_probe:
-            # the price of deterministic mode on this box, measured after the timed region: the same step re-captured
-            # with every reduction in a fixed order (partial rows + ordered summing launches instead of f32 atomics)
-            try:
-                L.set_deterministic(True)
-                trainer.capture(img, samples, warmup=2)
-                for _ in range(3):
-                    trainer.replay()
-                torch.cuda.synchronize(dev)
-                t1 = time.perf_counter()
-                for _ in range(10):
-                    trainer.replay()
-                torch.cuda.synchronize(dev)
-                out['deterministic_mode'] = {'ms_per_step': round((time.perf_counter() - t1) / 10 * 1e3, 3), 'steps': 10,
-                                             'default_ms_per_step': out['ms_per_step']}
-            except Exception as e:   # noqa: BLE001 -- a note, never the bench line
-                out['deterministic_mode'] = {'error': repr(e)}
-            finally:
-                L.set_deterministic(False)
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(mode, H, W, args.cpu_baseline_seconds)
-            try:
-                out['parity'] = bf16_parity(H, W, dev)
-            except Exception as e:   # noqa: BLE001 -- the parity note must never cost the bench line
-                out['parity'] = {'error': repr(e)}
-        if os.environ.get('LEDN_BENCH_VERBOSE'):
-            for e, v in sorted(fam.items(), key=lambda kv: -kv[1]['ms']):
-                print(f"{v['ms'] / k_steps:9.3f} ms/step  x{v['n'] // k_steps:4d}  {v['bytes'] / max(1e-9, v['ms']) / 1e6:8.1f} GB/s "
-                      f"{v['flops'] / max(1e-9, v['ms']) / 1e9:8.2f} TF/s  [kernel] {e}", file=sys.stderr)
-            verbose = os.environ['LEDN_BENCH_VERBOSE']
-            n_sig = int(verbose) if verbose.isdigit() and int(verbose) > 1 else 25     # signatures listed
-            for (e, sg), v in top[:n_sig]:
-                print(f'{v["ms"] / k_steps:9.3f} ms/step  x{v["n"] // k_steps:3d}  {v["bytes"] * v["n"] / max(1e-9, v["ms"]) / 1e6:8.1f} GB/s '
-                      f'{v["flops"] * v["n"] / max(1e-9, v["ms"]) / 1e9:8.2f} TF/s  {e} [{sg}] <{v["kernel"]}>', file=sys.stderr)
+        if args.full:
+            # ---- dominant kernel FUNCTION (as rocprofv3 --stats groups them, template instances merged)
+            # by summed HIP-event time; its roofline = the larger of its two time floors
+            # (algorithmic bytes / HBM peak, algorithmic flops / dense MFMA peak)
+            agg, fam = {}, {}
+            for r in launches:
+                k = (r['entry'], r['sig'])
+                a = agg.setdefault(k, dict(ms=0.0, n=0, bytes=r['bytes'], flops=r['flops'], kernel=r['kernel']))
+                a['ms'] += r['ms']
+                a['n'] += 1
+                f = fam.setdefault(r['kernel'], dict(ms=0.0, n=0, bytes=0, flops=0))
+                f['ms'] += r['ms']
+                f['n'] += 1
+                f['bytes'] += r['bytes']
+                f['flops'] += r['flops']
+            top = sorted(agg.items(), key=lambda kv: -kv[1]['ms'])
+            kname, f = max(fam.items(), key=lambda kv: kv[1]['ms'])
+            avg_ms = f['ms'] / f['n']
+            gbs = f['bytes'] / (f['ms'] * 1e-3) / 1e9
+            tfl = f['flops'] / (f['ms'] * 1e-3) / 1e12
+            peak_t = MFMA_PEAK_TFLOPS[args.dtype]
+            mfma_bound = f['flops'] / (peak_t * 1e12) > f['bytes'] / (HBM_PEAK_GBS * 1e9)
+            if mfma_bound:
+                roof = dict(bound='mfma', achieved=round(tfl, 3), peak=peak_t, unit='TFLOP/s', frac=round(tfl / peak_t, 5))
+            else:
+                roof = dict(bound='hbm', achieved=round(gbs, 1), peak=HBM_PEAK_GBS, unit='GB/s',
+                            frac=round(gbs / HBM_PEAK_GBS, 5))
+            roof['traffic'] = pmc_traffic(kname, mode, args.dtype)
+            roof['mfma_busy'] = pmc_record(kname, mode, args.dtype).get('mfma_busy_frac')   # SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x kernel cycles), same PMC collection
+            roof.update(kernel=kname, avg_us=round(avg_ms * 1e3, 2), launches_per_step=f['n'] // k_steps,
+                        alg_bytes_per_launch=f['bytes'] // f['n'], alg_flops_per_launch=f['flops'] // f['n'],
+                        alg_gbs=round(gbs, 1), alg_tflops=round(tfl, 3), mfma_frac=round(tfl / peak_t, 5),
+                        arithmetic_intensity=round(f['flops'] / max(1, f['bytes']), 1),
+                        share_of_gpu_time=round(f['ms'] / max(1e-9, sum(v['ms'] for v in fam.values())), 4))
+            # the other kernel functions by time, each against the same two roofs (the convolution work is spread over five
+            # matrix-core kernels since round 3: the dominant one alone no longer describes it)
+            roof['by_kernel'] = []
+            for kn, ff in sorted(fam.items(), key=lambda kv: -kv[1]['ms'])[:8]:
+                g_, t_ = ff['bytes'] / (ff['ms'] * 1e-3) / 1e9, ff['flops'] / (ff['ms'] * 1e-3) / 1e12
+                roof['by_kernel'].append(dict(kernel=kn, ms_per_step=round(ff['ms'] / k_steps, 3), launches_per_step=ff['n'] // k_steps,
+                                              avg_us=round(ff['ms'] / ff['n'] * 1e3, 2), alg_gbs=round(g_, 1), hbm_frac=round(g_ / HBM_PEAK_GBS, 4),
+                                              alg_tflops=round(t_, 2), mfma_frac=round(t_ / peak_t, 4)))
+            total_flops = sum(v['flops'] * v['n'] for k, v in agg.items() if k[0] in ('ledn_conv2d', 'ledn_conv2d_wgrad', 'ledn_window_attn'))
+            total_bytes = sum(v['bytes'] * v['n'] for v in agg.values())
+            gpu_ms = sum(v['ms'] for v in agg.values())
+            out['config'].update({
+                'collectives_per_step': (None if not coll_log else
+                                         sum(1 for c in coll_log if c[1] == 'all_reduce') // k_steps),
+                'collective_launches_per_step': (None if not coll_log else _coll_launches(coll_log) // k_steps),
+                'collective_bytes_per_step': (None if not coll_log else
+                                              4 * sum(c[2] for c in coll_log if c[1] == 'all_reduce') // k_steps),
+                'kernel_launches_per_step': len(launches) // k_steps,
+                'kernel_timing': 'HIP events on the launch streams, instrumented eager pass of the same step right after the timed region',
+                'conv_gemm_tflops_whole_step': round(total_flops / (gpu_ms * 1e-3) / 1e12, 3),
+                'hbm_alg_gbs_whole_step': round(total_bytes / (gpu_ms * 1e-3) / 1e9, 1),
+                'gpu_busy_frac': round(gpu_ms / k_steps / (dt / args.steps * 1e3), 3)})
+            out['roofline'] = roof
+            if mode == 'train' and world == 1 and graphed and not L.is_deterministic() and not args.no_det_probe:
+                # the price of deterministic mode on this box, measured after the timed region: the same step re-captured
+                # with every reduction in a fixed order (partial rows + ordered summing launches instead of f32 atomics)
+                try:
+                    L.set_deterministic(True)
+                    trainer.capture(img, samples, warmup=2)
+                    for _ in range(3):
+                        trainer.replay()
+                    torch.cuda.synchronize(dev)
+                    t1 = time.perf_counter()
+                    for _ in range(10):
+                        trainer.replay()
+                    torch.cuda.synchronize(dev)
+                    out['deterministic_mode'] = {'ms_per_step': round((time.perf_counter() - t1) / 10 * 1e3, 3), 'steps': 10,
+                                                 'default_ms_per_step': out['ms_per_step']}
+                except Exception as e:   # noqa: BLE001 -- a note, never the bench line
+                    out['deterministic_mode'] = {'error': repr(e)}
+                finally:
+                    L.set_deterministic(False)
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(mode, H, W, args.cpu_baseline_seconds)
+                try:
+                    out['parity'] = bf16_parity(H, W, dev)
+                except Exception as e:   # noqa: BLE001 -- the parity note must never cost the bench line
+                    out['parity'] = {'error': repr(e)}
+            if os.environ.get('LEDN_BENCH_VERBOSE'):
+                for e, v in sorted(fam.items(), key=lambda kv: -kv[1]['ms']):
+                    print(f"{v['ms'] / k_steps:9.3f} ms/step  x{v['n'] // k_steps:4d}  {v['bytes'] / max(1e-9, v['ms']) / 1e6:8.1f} GB/s "
+                          f"{v['flops'] / max(1e-9, v['ms']) / 1e9:8.2f} TF/s  [kernel] {e}", file=sys.stderr)
+                verbose = os.environ['LEDN_BENCH_VERBOSE']
+                n_sig = int(verbose) if verbose.isdigit() and int(verbose) > 1 else 25     # signatures listed
+                for (e, sg), v in top[:n_sig]:
+                    print(f'{v["ms"] / k_steps:9.3f} ms/step  x{v["n"] // k_steps:3d}  {v["bytes"] * v["n"] / max(1e-9, v["ms"]) / 1e6:8.1f} GB/s '
+                          f'{v["flops"] * v["n"] / max(1e-9, v["ms"]) / 1e9:8.2f} TF/s  {e} [{sg}] <{v["kernel"]}>', file=sys.stderr)
         print(json.dumps(out), file=real_stdout, flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -51,6 +51,20 @@ def golden_names(prefix):
                   if f.startswith(prefix) and f.endswith('.npz'))
 
 
+def config_digest(x):
+    """sha256 of a config value (dicts with sorted keys; lists and tuples kept apart): pins a mirrored section of
+    the reference's configs to the digest recorded from the reference's own file"""
+    import hashlib
+
+    def canon(v):
+        if isinstance(v, dict):
+            return {k: canon(v[k]) for k in sorted(v)}
+        if isinstance(v, (list, tuple)):
+            return type(v)(canon(e) for e in v)
+        return v
+    return hashlib.sha256(repr(canon(x)).encode()).hexdigest()
+
+
 # --------------------------------------------------------------------------- #
 # CPU emulation build of the kernel sources (tests only; see csrc/emu.h)
 # --------------------------------------------------------------------------- #

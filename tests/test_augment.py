@@ -248,8 +248,9 @@ def test_augmented_batch_feeds_the_train_step(be):
 
 
 def test_reference_dataset_pipelines_build():
-    """the train / test pipelines of configs/_base_/datasets/pascal_voc12.py:6-26 (values mirrored here: the GPU box
-    has no /root/reference) build into the GPU Compose with the reference's type names and arguments"""
+    """the train / test pipelines of configs/_base_/datasets/pascal_voc12.py:6-26 (values mirrored here, pinned by
+    digest to the pipelines of configs/LED_Net/LEDNet_80k_cityscapes-1024x1024.py as load_config reads them) build
+    into the GPU Compose with the reference's type names and arguments"""
     from led_net_amd import transforms as T
     train_pipeline = [
         dict(type='LoadImageFromFile'), dict(type='LoadAnnotations'),
@@ -261,11 +262,8 @@ def test_reference_dataset_pipelines_build():
     names = [type(t).__name__ for t in T.Compose(train_pipeline).transforms]
     assert names == ['RandomResize', 'RandomCrop', 'RandomFlip', 'PhotoMetricDistortion', 'PackSegInputs']
     assert [type(t).__name__ for t in T.Compose(test_pipeline).transforms] == ['Resize', 'PackSegInputs']
-    ref = '/root/reference/configs/LED_Net/LEDNet_80k_cityscapes-1024x1024.py'
-    import os
-    if os.path.exists(ref):            # in the build container: the reference's own file, unchanged
-        import led_net_amd as L
-        cfg = L.load_config(ref)
-        assert [c['type'] for c in cfg['train_pipeline']] == [c['type'] for c in train_pipeline]
-        T.Compose(cfg['train_pipeline'])
-        T.Compose(cfg['test_pipeline'])
+    # digests of cfg['train_pipeline'] and cfg['test_pipeline'] of the reference's config: the mirrored lists are
+    # those pipelines, unchanged, so the Compose built above is the one the reference's file builds
+    from conftest import config_digest
+    assert config_digest(train_pipeline) == '576e041922fa2bb3450fe2f34537ff9c8398f1ad13718a76daf38817b9c5aee4'
+    assert config_digest(test_pipeline) == '93e99646ebf5a268434a1ce8d864952904627c0de5a9cec9a066b4a7265cd2d8'

@@ -1,5 +1,5 @@
-"""bench.py: the driver contract (one JSON line on stdout, the keys the driver reads, `roofline` / `cpu_baseline`
-objects) and the multi-rank launcher's refusals."""
+"""bench.py: the driver contract (one JSON line on stdout, the keys the driver reads; `roofline` / `cpu_baseline`
+objects with --full), --dump-outputs, and the multi-rank launcher's refusals."""
 import json
 import os
 import subprocess
@@ -39,7 +39,7 @@ def test_world_size_mismatch_is_an_error():
 @pytest.mark.gpu
 @pytest.mark.parametrize('mode', ['train', 'infer'])
 def test_bench_prints_one_json_line_with_the_contract_keys(mode):
-    r = _run(['--steps', '3', '--warmup', '1', '--mode', mode, '--cpu-baseline-seconds', '2'], timeout=900)
+    r = _run(['--steps', '3', '--warmup', '1', '--mode', mode, '--cpu-baseline-seconds', '2', '--full'], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[:1000]
@@ -54,3 +54,78 @@ def test_bench_prints_one_json_line_with_the_contract_keys(mode):
     assert abs(rf['frac'] - rf['achieved'] / rf['peak']) < 1e-3 and 'traffic' in rf and rf['kernel']
     cb = d['cpu_baseline']
     assert cb['kind'] == 'port' and cb['value'] > 0 and cb['cores'] >= 1 and cb['sample']
+
+
+def test_steps_must_be_positive():
+    r = _run(['--steps', '0', '--warmup', '0'], timeout=120)
+    assert r.returncode != 0 and '--steps' in r.stderr and r.stdout.strip() == ''
+
+
+def test_dump_outputs_stays_within_budget_and_samples_the_same_positions(tmp_path, monkeypatch):
+    """arrays that do not fit are replaced by the same seeded sample of their elements in every run, drawn from a
+    generator of its own (the process's global random stream is left as it was).  A small budget stands in for the
+    64 MB one: same code path, no large allocations in the test process."""
+    import numpy as np
+    import torch
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 6000)
+    g = torch.Generator().manual_seed(11)
+    logits = torch.randn(2, 2, 16, 32, generator=g)
+    mask = torch.randint(0, 2, (2, 16, 32), dtype=torch.uint8, generator=g)
+    rng = torch.get_rng_state()
+    runs = []
+    for d in ('a', 'b'):
+        bench.dump_outputs(bench.step_outputs('infer', (logits, mask), None), str(tmp_path / d))
+        runs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    assert torch.equal(torch.get_rng_state(), rng)
+    assert sorted(runs[0]) == ['pred_sem_seg.npy', 'seg_logits.npy']
+    for f, a in runs[0].items():
+        assert a.dtype == np.float32 and a.size == 6000 // 2 // 4 and np.array_equal(a, runs[1][f])
+    assert sum(a.nbytes for a in runs[0].values()) <= 6000
+    assert np.isin(runs[0]['seg_logits.npy'], logits.numpy()).all()
+    small = {'decode.loss_context': torch.tensor(1.5), 'parameters': torch.arange(10, dtype=torch.float64)}
+    bench.dump_outputs(small, str(tmp_path / 'c'))
+    assert np.load(tmp_path / 'c' / 'decode.loss_context.npy') == np.float32(1.5)
+    p = np.load(tmp_path / 'c' / 'parameters.npy')
+    assert p.dtype == np.float64 and np.array_equal(p, np.arange(10))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('mode', ['train', 'infer'])
+def test_plain_bench_times_the_steps_and_dumps_reproducible_outputs(mode, tmp_path):
+    """a plain run prints the contract keys without the --full measurements; --dump-outputs writes the same outputs in
+    every run, whatever the number of steps timed before: inference the last timed step (no state), training one step
+    of the timed path from the run's start state.  Bounds relative to each array's largest magnitude: training 1e-2
+    (bf16 activations, atomics-ordered sums: two runs measured 1.1e-3 in the parameters, 2e-4 in the loss), inference
+    1e-5 (measured bit-identical)."""
+    import numpy as np
+    dumps = []
+    for steps, warmup in ((2, 1), (3, 2)):
+        out = tmp_path / f'out{steps}'
+        r = _run(['--steps', str(steps), '--warmup', str(warmup), '--mode', mode, '--dump-outputs', str(out)], timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[:1000]
+        d = json.loads(lines[0])
+        assert d['steps'] == steps and d['warmup'] == warmup and d['ms_per_step'] > 0 and d['value'] > 0
+        assert d['unit'] == 'images/s' and d['higher_is_better'] is True and d['dtype'] == 'bf16'
+        assert abs(d['value'] - d['config']['global_batch'] / (d['ms_per_step'] * 1e-3)) < 0.02 * d['value']
+        assert not {'roofline', 'cpu_baseline', 'parity', 'deterministic_mode'} & set(d)
+        files = sorted(os.listdir(out))
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10 ** 6
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        if mode == 'train':
+            assert {'decode.loss_context', 'decode.loss_spatial', 'parameters', 'buffers'} <= set(arrays)
+            assert arrays['decode.loss_context'] > 0
+        else:
+            assert set(arrays) == {'seg_logits', 'pred_sem_seg'}
+            assert set(np.unique(arrays['pred_sem_seg'])) <= {0.0, 1.0}
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    tol = 1e-2 if mode == 'train' else 1e-5
+    for k, a in dumps[0].items():
+        b = dumps[1][k].astype(np.float64)
+        a = a.astype(np.float64)
+        assert np.abs(a - b).max() <= tol * max(np.abs(a).max(), 1e-30), (k, np.abs(a - b).max(), np.abs(a).max())

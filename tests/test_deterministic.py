@@ -32,14 +32,14 @@ def _setup(dev, dtype, hw=(320, 320), nb=2, seed=5):
     return L, model, cfg, img, samples
 
 
-def test_deterministic_mode_reaches_no_float_atomic(monkeypatch):
+def test_deterministic_mode_reaches_no_float_atomic(monkeypatch, tmp_path):
     """one bf16 image at 320 x 320 (reflect-padded attention windows, every small-map reduction of the context branch):
     the emulator counts float atomicAdd call sites; the default mode goes through dozens, deterministic mode through none"""
     import atomic_census
     import led_net_amd as L
     L.set_deterministic(True)
     try:
-        n, txt = atomic_census.census('bf16', (320, 320), 1, steps=2, out='/tmp/ledn_census_det_test.txt')
+        n, txt = atomic_census.census('bf16', (320, 320), 1, steps=2, out=str(tmp_path / 'census.txt'))
     finally:
         L.set_deterministic(False)
     assert n == 0, f'deterministic mode still reaches float atomics:\n{txt}'

@@ -10,6 +10,6 @@ fi
 i=0
 for V in "$@"; do
   i=$((i+1)); [ "$V" = "-" ] && V=""
-  env $V LEDN_BENCH_VERBOSE=60 timeout -k 10 400 python bench.py --steps 40 --warmup 5 --no-cpu-baseline > $OUT/v$i.json 2> $OUT/v$i.err || { echo "variant $i failed"; tail -5 $OUT/v$i.err; exit 1; }
+  env $V LEDN_BENCH_VERBOSE=60 timeout -k 10 400 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline > $OUT/v$i.json 2> $OUT/v$i.err || { echo "variant $i failed"; tail -5 $OUT/v$i.err; exit 1; }
   echo "variant $i [$V]: $(python -c "import json; d=json.load(open('$OUT/v$i.json')); print(d['value'], 'img/s', d['ms_per_step'], 'ms', d['config']['kernel_launches_per_step'], 'launches')")"
 done

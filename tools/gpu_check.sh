@@ -11,7 +11,7 @@ tail -15 $OUT/pytest_gpu.log
 timeout 600 python __graft_entry__.py --incremental smoke > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -6 $OUT/smoke.log
 for MODE in train infer; do
   for DT in bf16 f32; do
-    LEDN_BENCH_VERBOSE=1 timeout 1200 python bench.py --mode $MODE --steps 4 --warmup 2 --dtype $DT > $OUT/bench_${MODE}_$DT.json 2> $OUT/bench_${MODE}_$DT.err
+    LEDN_BENCH_VERBOSE=1 timeout 1200 python bench.py --full --mode $MODE --steps 4 --warmup 2 --dtype $DT > $OUT/bench_${MODE}_$DT.json 2> $OUT/bench_${MODE}_$DT.err
     echo "bench $MODE $DT rc=$?"; cat $OUT/bench_${MODE}_$DT.json; grep -v amdgpu.ids $OUT/bench_${MODE}_$DT.err | head -40
   done
 done

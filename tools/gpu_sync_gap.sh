@@ -5,7 +5,7 @@ TAG=${1:-gap}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT; export TMPDI
 python __graft_entry__.py --incremental > $OUT/build.log 2>&1 || { tail -20 $OUT/build.log; exit 1; }
 run() { # name, env..., -- args
   name=$1; shift
-  env "$@" timeout -k 10 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline $ARGS > $OUT/$name.json 2> $OUT/$name.err || { tail -5 $OUT/$name.err; exit 1; }
+  env "$@" timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $ARGS > $OUT/$name.json 2> $OUT/$name.err || { tail -5 $OUT/$name.err; exit 1; }
   python -c "import json; d=json.loads(open('$OUT/$name.json').read().strip().splitlines()[-1]); print('$name', d['value'], d['ms_per_step'], d['config'].get('collective_launches_per_step'))"
 }
 ARGS=""; run plain A=1 || exit 1

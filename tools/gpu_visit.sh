@@ -9,7 +9,7 @@ if [ "$2" != "-" ]; then
 fi
 if [ -n "$3" ]; then timeout -k 10 300 python tools/conv_bench.py 2>&1 | grep -v amdgpu.ids | tee $OUT/conv_bench.txt || exit 1; fi
 if [ -n "$4" ]; then
-  LEDN_BENCH_VERBOSE=400 timeout -k 10 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_train.json 2> $OUT/bench_train.err || { tail -5 $OUT/bench_train.err; exit 1; }
+  LEDN_BENCH_VERBOSE=400 timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_train.json 2> $OUT/bench_train.err || { tail -5 $OUT/bench_train.err; exit 1; }
   cat $OUT/bench_train.json; grep "ms/step" $OUT/bench_train.err | head -60
 fi
 if [ -n "$5" ]; then timeout -k 10 300 python tools/conv_bench.py $5 2>&1 | grep -v amdgpu.ids | tee $OUT/conv_bench_ab.txt || exit 1; fi

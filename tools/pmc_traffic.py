@@ -88,7 +88,7 @@ def main():
     ap.add_argument('--no-mfma-pass', action='store_true')
     args = ap.parse_args()
     bench_args = ['--mode', args.mode, '--dtype', args.dtype, '--steps', '1', '--warmup', '1',
-                  '--no-cpu-baseline', '--no-graph']
+                  '--no-cpu-baseline', '--no-graph', '--full']
     tag = f'{args.mode}_{args.dtype}'
     fetch = run_pass(['FETCH_SIZE'], os.path.join(args.scratch, tag, 'fetch'), bench_args)
     write = run_pass(['WRITE_SIZE'], os.path.join(args.scratch, tag, 'write'), bench_args)

@@ -16,7 +16,7 @@ run() {   # name, N, env assignments..., -- bench flags...
   local name=$1 n=$2; shift 2
   local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
   local f="$OUT/${name}_n${n}.json"
-  env "${envs[@]}" timeout -k 10 900 python bench.py --gpus "$n" --steps "$STEPS" --warmup 5 --no-cpu-baseline "$@" > "$f" 2> "$OUT/${name}_n${n}.err" \
+  env "${envs[@]}" timeout -k 10 900 python bench.py --full --gpus "$n" --steps "$STEPS" --warmup 5 --no-cpu-baseline "$@" > "$f" 2> "$OUT/${name}_n${n}.err" \
     || { echo "$name N=$n FAILED (see $OUT/${name}_n${n}.err)" | tee -a "$OUT/table.txt"; return 0; }
 }
 for n in 1 2 4 8; do
