@@ -481,6 +481,49 @@ int ledn_iou_hist(const unsigned char* pred, const long long* label, long long P
                   int ignore_index, float* hist, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Merging inference results at the original resolution: test-time augmentation and sliding windows.
+ * Accumulators are PLANAR f32 ([C][Ho][Wo] / [N][C][H][W]); C in {2, 3, 4, 5, 8, 19}, anything else LEDN_EINVAL.
+ * Every output element has one writer per launch and launches on one stream are ordered: results are
+ * deterministic without atomics.
+ * ------------------------------------------------------------------------- */
+enum { LEDN_FLIP_NONE = 0, LEDN_FLIP_HORIZONTAL = 1, LEDN_FLIP_VERTICAL = 2 };
+enum { LEDN_TTA_SOFTMAX = 0, LEDN_TTA_RAW = 1 };
+/* One view of one image into the image's accumulator.  Per output pixel: the valid region [0,hv) x [0,wv) of the
+ * view's logits (the rest is right/bottom batch padding) is un-flipped and sampled bilinearly (align_corners=False,
+ * the arithmetic of ledn_bilinear; the identity when (hv, wv) == (Ho, Wo)), then v = softmax over C (f32,
+ * max-subtracted; LEDN_TTA_SOFTMAX) or the logits themselves (LEDN_TTA_RAW), then acc = (first ? 0 : acc) + v; with
+ * `last`, acc / K is written instead and, if mask != NULL, its first-max channel index.  K views = K launches, no
+ * zeroing pass and no argmax pass.
+ * Replaces, per view, postprocess_result's crop / flip / resize (mmseg/models/segmentors/base.py:160-186) plus
+ * SegTTAModel.merge_preds (segmentors/seg_tta.py:28-40); LEDN_TTA_RAW: EncoderDecoder.aug_test
+ * (segmentors/encoder_decoder.py:347-364). */
+typedef struct {
+    const float* src;      /* the view's logits: [Hs,Ws,C] (NHWC) or, with src_planar, [C,Hs,Ws] */
+    float* acc;            /* [C,Ho,Wo] */
+    unsigned char* mask;   /* optional [Ho,Wo], written by the `last` launch */
+    int Hs, Ws;            /* extent of src */
+    int hv, wv;            /* valid extent: 0 < hv <= Hs, 0 < wv <= Ws */
+    int C, Ho, Wo;
+    int src_planar;
+    int flip;              /* LEDN_FLIP_*: how the view was flipped (undone here) */
+    int mode;              /* LEDN_TTA_* */
+    int first, last;       /* first / last view of the image */
+    int K;                 /* number of views (the divisor of the `last` launch) */
+} ledn_tta_desc;
+int ledn_tta_accumulate(const ledn_tta_desc* d, void* stream);
+/* canvas[N,C,H,W][:, :, y1:y1+hc, x1:x1+wc] += crop, crop = the f32 logits of one window, [N,hc,wc,C] or, with
+ * crop_planar, [N,C,hc,wc].  The caller zeroes the canvas before the first window.  Replaces
+ * preds += F.pad(crop_seg_logit, ...) (segmentors/encoder_decoder.py:284-286) without the padded tensor. */
+int ledn_slide_accumulate(float* canvas, const float* crop, int N, int C, int H, int W, int y1, int x1, int hc, int wc,
+                          int crop_planar, void* stream);
+/* canvas[n,c,y,x] /= (float)(rowcnt[y] * colcnt[x]) in place, and the first-max channel index of the quotient to
+ * mask [N,H,W] (optional).  rowcnt [H] / colcnt [W]: int32 DEVICE arrays, the number of windows that cover a row /
+ * a column -- the reference's count_mat (encoder_decoder.py:269,288-290) is their outer product.  The caller checks
+ * on the host, where it builds them, that no count is zero (the reference's assert (count_mat == 0).sum() == 0). */
+int ledn_slide_finish(float* canvas, const int* rowcnt, const int* colcnt, unsigned char* mask, int N, int C, int H,
+                      int W, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * SEAM edge map (prototype tools/speed/ddrnet_speed.py:24-37,282-338; percentile
  * rule: supplementary PDF section 4.2 eq.1).
  *   seg [N,h,w] f32 -> per-image min-max normalise -> Laplacian at strides 1/2/4,

@@ -109,6 +109,16 @@ class ResizeDesc(C.Structure):
                 ('out_nchw', i32), ('dtype_x', i32), ('dtype_y', i32)]
 
 
+class TtaDesc(C.Structure):            # mirrors ledn_tta_desc
+    _fields_ = [('src', fp), ('acc', fp), ('mask', vp), ('Hs', i32), ('Ws', i32), ('hv', i32), ('wv', i32),
+                ('C', i32), ('Ho', i32), ('Wo', i32), ('src_planar', i32), ('flip', i32), ('mode', i32),
+                ('first', i32), ('last', i32), ('K', i32)]
+
+
+FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 0, 1, 2
+TTA_SOFTMAX, TTA_RAW = 0, 1
+
+
 class MfafDesc(C.Structure):
     _fields_ = [('x', vp), ('r', vp), ('xl', vp), ('ctx', fp * 4), ('ctx_size', i32 * 4),
                 ('scale', fp * 5), ('shift', fp * 5), ('out', vp),
@@ -223,6 +233,9 @@ _PROTOS = {
     'ledn_affine_act': ([C.POINTER(AffineDesc), vp], i32),
     'ledn_nchw_to_nhwc': ([vp, i32, vp, i32, i32, i32, i32, i32, fp, fp, vp, vp, C.c_float, vp], i32),
     'ledn_bilinear': ([C.POINTER(ResizeDesc), vp], i32),
+    'ledn_tta_accumulate': ([C.POINTER(TtaDesc), vp], i32),
+    'ledn_slide_accumulate': ([fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    'ledn_slide_finish': ([fp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
     'ledn_adaptive_avgpool': ([vp, vp, fp, i32, i32, i32, i32, i32, i32, vp], i32),
     'ledn_relpos_bias': ([fp, vp, fp, i32, i32, i32, vp], i32),
     'ledn_relpos_bias_bwd': ([fp, vp, fp, i32, i32, i32, vp], i32),

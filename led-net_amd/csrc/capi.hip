@@ -125,6 +125,11 @@ int ohem_ce_up_bwd_impl(const float* src, int N, int Hs, int Ws, int H, int W, c
 int ohem_ce_bwd_impl(const float* logits, const long long* target, long long P, int C, int ignore_label,
                      const float* work, const float* out, const float* dloss, float loss_weight,
                      float* dlogits, hipStream_t s);
+int tta_accumulate_impl(const ledn_tta_desc& d, hipStream_t s);
+int slide_accumulate_impl(float* canvas, const float* crop, int N, int C, int H, int W, int y1, int x1, int hc, int wc,
+                          int crop_planar, hipStream_t s);
+int slide_finish_impl(float* canvas, const int* rowcnt, const int* colcnt, unsigned char* mask, int N, int C, int H,
+                      int W, hipStream_t s);
 int sgd_step_impl(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,
                   const float* lr_dev, float momentum, float weight_decay, float grad_scale, hipStream_t s);
 }  // namespace ledn
@@ -413,6 +418,15 @@ int ledn_aug_crop_hist(const ledn_aug_entry* table_dev, int n, int max_pixels, i
     return aug_crop_hist_impl(table_dev, n, max_pixels, hist, S(stream));
 }
 int ledn_bilinear(const ledn_resize_desc* d, void* stream) { return d ? bilinear_impl(*d, S(stream)) : LEDN_EINVAL; }
+int ledn_tta_accumulate(const ledn_tta_desc* d, void* stream) { return d ? tta_accumulate_impl(*d, S(stream)) : LEDN_EINVAL; }
+int ledn_slide_accumulate(float* canvas, const float* crop, int N, int C, int H, int W, int y1, int x1, int hc, int wc,
+                          int crop_planar, void* stream) {
+    return slide_accumulate_impl(canvas, crop, N, C, H, W, y1, x1, hc, wc, crop_planar, S(stream));
+}
+int ledn_slide_finish(float* canvas, const int* rowcnt, const int* colcnt, unsigned char* mask, int N, int C, int H,
+                      int W, void* stream) {
+    return slide_finish_impl(canvas, rowcnt, colcnt, mask, N, C, H, W, S(stream));
+}
 int ledn_adaptive_avgpool(const void* x, const void* xadd, float* y, int N, int H, int W, int C, int Sz,
                           int dtype, void* stream) {
     return adaptive_avgpool_impl(x, xadd, y, N, H, W, C, Sz, dtype, S(stream));

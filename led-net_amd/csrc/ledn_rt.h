@@ -247,7 +247,15 @@ struct Lerp {
 };
 __device__ __forceinline__ Lerp lerp_coord(int dst, int in, int out) {
     const float scale = (float)in / (float)out;
+#ifdef LEDN_CPU_EMU
+    // the device compiler contracts this into ONE fused multiply-add (one rounding, as ATen's kernels); the host build
+    // has no contraction of its own, and above coordinate 64 a second rounding moves a lerp weight by 7.6e-6.  (An
+    // explicit fmaf in the device build reorders the lerp of existing kernels; should the compiler ever stop
+    // contracting this line, tests/test_slide_tta.py's geometry cases on the HIP build miss their bound.)
+    float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
+#else
     float src = scale * ((float)dst + 0.5f) - 0.5f;
+#endif
     if (src < 0.f) src = 0.f;
     Lerp l;
     l.i0 = (int)src;

@@ -848,3 +848,87 @@ def seam_edge(seg, percentile=0.8, thr=0.1, final_thr=0.1):
     _run(lib, 'ledn_seam_edge', seg, _p(seg), _p(edge), _p(scratch), N, h, w, kth, thr, final_thr,
          work=_TIMING is not None and (f'seam {N}x{h}x{w}', _nb(seg, edge), 60 * seg.numel()))
     return edge
+
+
+_FLIP = {None: _lib.FLIP_NONE, False: _lib.FLIP_NONE, 'horizontal': _lib.FLIP_HORIZONTAL, 'vertical': _lib.FLIP_VERTICAL}
+MERGE_CHANNELS = (2, 3, 4, 5, 8, 19)      # the class counts tta_merge.hip is instantiated for
+
+
+def _merge_c(name, Cc):
+    if Cc not in MERGE_CHANNELS:
+        raise LednError(f'{name}: {Cc} classes unsupported (kernels exist for {MERGE_CHANNELS})')
+
+
+def tta_accumulate(src, acc, *, first, last, K, valid=None, flip=None, planar=False, mode='softmax', mask=None):
+    """One test-time-augmentation view of one image into its accumulator (ledn_tta_accumulate).
+
+    src: f32 logits of the view, [Hs,Ws,C] or (planar) [C,Hs,Ws]; valid = (hv, wv): the part that is not batch padding;
+    flip: None | 'horizontal' | 'vertical' (undone here); acc: f32 [C,Ho,Wo], OVERWRITTEN when first, divided by K when
+    last; mask: uint8 [Ho,Wo], written when last.  mode 'softmax' (SegTTAModel.merge_preds) or 'raw' (aug_test)."""
+    lib = _lib.get_lib()
+    if src.dim() != 3 or acc.dim() != 3 or src.dtype != torch.float32 or acc.dtype != torch.float32:
+        raise LednError('tta_accumulate: src and acc must be 3-d float32 tensors')
+    Cc, Ho, Wo = acc.shape
+    Hs, Ws, Cs = (src.shape[1], src.shape[2], src.shape[0]) if planar else src.shape
+    if Cs != Cc:
+        raise LednError(f'tta_accumulate: the view has {Cs} classes, the accumulator {Cc}')
+    _merge_c('tta_accumulate', Cc)
+    hv, wv = (Hs, Ws) if valid is None else (int(valid[0]), int(valid[1]))
+    if not (0 < hv <= Hs and 0 < wv <= Ws):
+        raise LednError(f'tta_accumulate: valid extent {(hv, wv)} outside the view {(Hs, Ws)}')
+    if flip not in _FLIP or mode not in ('softmax', 'raw') or int(K) < 1:
+        raise LednError(f'tta_accumulate: flip={flip!r} mode={mode!r} K={K!r}')
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (Ho, Wo)):
+        raise LednError('tta_accumulate: mask must be uint8 [Ho,Wo]')
+    if mask is not None and not last:
+        raise LednError('tta_accumulate: the mask is written by the last view only')
+    _check(lib, src, acc, mask)
+    d = _lib.TtaDesc()
+    d.src, d.acc, d.mask = _p(src), _p(acc), _p(mask)
+    d.Hs, d.Ws, d.hv, d.wv, d.C, d.Ho, d.Wo = Hs, Ws, hv, wv, Cc, Ho, Wo
+    d.src_planar, d.flip, d.mode = int(bool(planar)), _FLIP[flip], _lib.TTA_SOFTMAX if mode == 'softmax' else _lib.TTA_RAW
+    d.first, d.last, d.K = int(bool(first)), int(bool(last)), int(K)
+    _run(lib, 'ledn_tta_accumulate', acc, d, work=_TIMING is not None and (
+        f'tta_acc C{Cc} {hv}x{wv}->{Ho}x{Wo}', _nb(src, mask) + acc.numel() * 4 * (1 if first else 2), 12 * acc.numel(),
+        'tta_accumulate_kernel'))
+    return acc
+
+
+def slide_accumulate(canvas, crop, y1, x1, planar=False):
+    """canvas[N,C,H,W][:, :, y1:y1+hc, x1:x1+wc] += crop (f32 logits of one window, [N,hc,wc,C] or planar [N,C,hc,wc])"""
+    lib = _lib.get_lib()
+    if canvas.dim() != 4 or crop.dim() != 4 or canvas.dtype != torch.float32 or crop.dtype != torch.float32:
+        raise LednError('slide_accumulate: canvas and crop must be 4-d float32 tensors')
+    N, Cc, H, W = canvas.shape
+    n, hc, wc, cc = (crop.shape[0], crop.shape[2], crop.shape[3], crop.shape[1]) if planar else crop.shape
+    if (n, cc) != (N, Cc):
+        raise LednError(f'slide_accumulate: crop batch / classes {(n, cc)} != canvas {(N, Cc)}')
+    _merge_c('slide_accumulate', Cc)
+    y1, x1 = int(y1), int(x1)
+    if y1 < 0 or x1 < 0 or y1 + hc > H or x1 + wc > W:
+        raise LednError(f'slide_accumulate: window {(y1, x1, hc, wc)} outside the canvas {(H, W)}')
+    _check(lib, canvas, crop)
+    _run(lib, 'ledn_slide_accumulate', canvas, _p(canvas), _p(crop), N, Cc, H, W, y1, x1, hc, wc, int(bool(planar)),
+         work=_TIMING is not None and (f'slide_acc C{Cc} {hc}x{wc}@{y1},{x1}', 3 * _nb(crop), crop.numel(), 'slide_accumulate_kernel'))
+    return canvas
+
+
+def slide_finish(canvas, rowcnt, colcnt):
+    """canvas /= outer(rowcnt, colcnt) in place; -> the first-max uint8 argmax [N,H,W].  rowcnt [H] / colcnt [W]: HOST
+    int32 tensors (windows per row / column); a zero count is refused here, before anything is launched."""
+    lib = _lib.get_lib()
+    if canvas.dim() != 4 or canvas.dtype != torch.float32:
+        raise LednError('slide_finish: canvas must be a 4-d float32 tensor')
+    N, Cc, H, W = canvas.shape
+    _merge_c('slide_finish', Cc)
+    for t, n in ((rowcnt, H), (colcnt, W)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or t.is_cuda:
+            raise LednError('slide_finish: rowcnt [H] / colcnt [W] must be host int32 tensors')
+    if int(rowcnt.min()) < 1 or int(colcnt.min()) < 1:
+        raise LednError('slide_finish: invalid argument: a pixel is covered by no window (count 0)')
+    rc, cc = rowcnt.contiguous().to(canvas.device), colcnt.contiguous().to(canvas.device)
+    mask = torch.empty((N, H, W), dtype=torch.uint8, device=canvas.device)
+    _check(lib, canvas, rc, cc, mask)
+    _run(lib, 'ledn_slide_finish', canvas, _p(canvas), _p(rc), _p(cc), _p(mask), N, Cc, H, W,
+         work=_TIMING is not None and (f'slide_fin C{Cc} {N}x{H}x{W}', 2 * _nb(canvas) + _nb(mask), 2 * canvas.numel(), 'slide_finish_kernel'))
+    return mask

@@ -210,6 +210,8 @@ class EncoderDecoder(nn.Module):
 
     # ---- encoder_decoder.py:187-222 (whole inference) + base.py:127-200
     def predict(self, inputs, data_samples=None):
+        if self.test_cfg.get('mode', 'whole') != 'whole':
+            return self._predict_slide(inputs, data_samples)
         feats = self.extract_feat(inputs, data_samples)
         H, W = inputs.shape[2:]
         plain = data_samples is None or all(
@@ -224,6 +226,94 @@ class EncoderDecoder(nn.Module):
                 ds.pred_sem_seg = PixelData(data=mask[i:i + 1])
             return data_samples
         return self.postprocess_result(self.decode_head.predict_nhwc(feats), data_samples)
+
+    # ---- encoder_decoder.py:241-345 (slide / whole inference)
+    def _is_plain(self, hw, data_samples):
+        """nothing to crop / flip / resize after the network"""
+        return data_samples is None or all(
+            not any(self._padding(ds)) and not ds.metainfo.get('flip')
+            and tuple(ds.metainfo.get('ori_shape', hw)[:2]) == tuple(hw) for ds in data_samples)
+
+    def _encode_decode_window(self, crop_img, metas):
+        """``encode_decode`` of one sliding window; a window that holds batch padding (``img_padding_size`` of its
+        metas) has it filled by the stem's input kernel like a padded whole image (a window wholly inside the
+        padding has the valid extent 0: the kernel then emits ``pad_val`` everywhere)"""
+        samples = [SegDataSample(metainfo=m) for m in metas] if metas else None
+        if samples is None or not any(any(self._padding(ds)) for ds in samples):
+            return self.encode_decode(crop_img, metas)
+        return self.decode_head.predict(self.extract_feat(crop_img, samples), metas, self.test_cfg)
+
+    def slide_grid(self, h_img, w_img):
+        """the window boxes (y1, y2, x1, x2) of encoder_decoder.py:262-277, in the reference's order, and the number
+        of windows over each row / column (``count_mat`` is the outer product of the two)"""
+        cfg = self.test_cfg
+        for key in ('crop_size', 'stride'):
+            v = cfg.get(key)
+            if not (isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, int) and e > 0 for e in v)):
+                raise ValueError(f"test_cfg mode='slide' needs {key}=(h, w) with positive integers, got {v!r}")
+        (h_stride, w_stride), (h_crop, w_crop) = cfg['stride'], cfg['crop_size']
+        h_grids = max(h_img - h_crop + h_stride - 1, 0) // h_stride + 1
+        w_grids = max(w_img - w_crop + w_stride - 1, 0) // w_stride + 1
+        boxes = []
+        rowcnt, colcnt = torch.zeros(h_img, dtype=torch.int32), torch.zeros(w_img, dtype=torch.int32)
+        for h_idx in range(h_grids):
+            y2 = min(h_idx * h_stride + h_crop, h_img)
+            y1 = max(y2 - h_crop, 0)
+            rowcnt[y1:y2] += 1
+            for w_idx in range(w_grids):
+                x2 = min(w_idx * w_stride + w_crop, w_img)
+                x1 = max(x2 - w_crop, 0)
+                boxes.append((y1, y2, x1, x2))
+                if h_idx == 0:
+                    colcnt[x1:x2] += 1
+        return boxes, rowcnt, colcnt
+
+    def slide_inference(self, inputs, batch_img_metas=None, return_mask=False):
+        """Inference by sliding windows with overlap (encoder_decoder.py:241-292): every window's logits are added
+        into a planar canvas (ledn_slide_accumulate; the padded tensor of the reference's F.pad never exists), one
+        pass divides by the window count and takes the argmax (ledn_slide_finish).  A crop larger than the image
+        uses the small patch unpadded.  -> N x C x H x W f32 logits (and the uint8 mask N x H x W)."""
+        N, _, h_img, w_img = inputs.shape
+        boxes, rowcnt, colcnt = self.slide_grid(h_img, w_img)
+        canvas = torch.zeros((N, self.out_channels, h_img, w_img), dtype=torch.float32, device=inputs.device)
+        pads = [self._padding(SegDataSample(metainfo=m)) for m in batch_img_metas] if batch_img_metas else None
+        for y1, y2, x1, x2 in boxes:
+            crop_img = inputs[:, :, y1:y2, x1:x2].contiguous()
+            metas = None
+            if batch_img_metas:      # change the image shape to patch shape; the window's share of the batch padding
+                metas = [dict(m, img_shape=(y2 - y1, x2 - x1),
+                              img_padding_size=(0, min(max(x2 - (w_img - p[1]), 0), x2 - x1), 0,
+                                                min(max(y2 - (h_img - p[3]), 0), y2 - y1)))
+                         for m, p in zip(batch_img_metas, pads)]
+            # planar window logits from the same last resize as whole inference: one window == whole, bit for bit
+            ops.slide_accumulate(canvas, self._encode_decode_window(crop_img, metas), y1, x1, planar=True)
+        mask = ops.slide_finish(canvas, rowcnt, colcnt)
+        return (canvas, mask) if return_mask else canvas
+
+    def whole_inference(self, inputs, batch_img_metas=None):
+        return self.encode_decode(inputs, batch_img_metas)
+
+    def inference(self, inputs, batch_img_metas=None):
+        """encoder_decoder.py:316-345: N x C x H x W logits of the (padded, possibly flipped) inputs"""
+        mode = self.test_cfg.get('mode', 'whole')
+        assert mode in ['slide', 'whole'], f'Only "slide" or "whole" test mode are supported, but got {mode}.'
+        if mode == 'slide':
+            return self.slide_inference(inputs, batch_img_metas)
+        return self.whole_inference(inputs, batch_img_metas)
+
+    def _predict_slide(self, inputs, data_samples=None):
+        mode = self.test_cfg.get('mode', 'whole')
+        assert mode in ['slide', 'whole'], f'Only "slide" or "whole" test mode are supported, but got {mode}.'
+        metas = [ds.metainfo for ds in data_samples] if data_samples is not None else None
+        logits, mask = self.slide_inference(inputs, metas, return_mask=True)
+        if not self._is_plain(inputs.shape[2:], data_samples):
+            return self.postprocess_result(logits.permute(0, 2, 3, 1).contiguous(), data_samples)
+        if data_samples is None:
+            data_samples = [SegDataSample() for _ in range(inputs.shape[0])]
+        for i, ds in enumerate(data_samples):
+            ds.seg_logits = PixelData(data=logits[i])
+            ds.pred_sem_seg = PixelData(data=mask[i:i + 1])
+        return data_samples
 
     def postprocess_result(self, seg_logits, data_samples=None):
         """base.py:127-200 on the fused NHWC f32 logits: per image remove the batch padding, undo the test-time
@@ -262,3 +352,88 @@ class EncoderDecoder(nn.Module):
         if mode == 'tensor':
             return self._forward(inputs, data_samples)
         raise RuntimeError(f'Invalid mode "{mode}". Only supports loss, predict and tensor mode')
+
+
+@MODELS.register_module()
+class SegTTAModel(nn.Module):
+    """mmseg/models/segmentors/seg_tta.py + mmengine's BaseTTAModel for the LED-Net path: the views of an image
+    (TestTimeAug: scales x flips) are predicted one after another and merged at the original resolution -- softmax of
+    every view's logits resized to ``ori_shape``, mean, argmax.
+
+    ``test_step`` never holds a view's logits at the original size: per view the network runs at the view's size and
+    ONE ``ops.tta_accumulate`` (un-pad, un-flip, resize, softmax, add; mean and argmax with the last view) goes
+    straight into the image's accumulator.  ``merge_preds`` on samples that already carry ``seg_logits`` uses the same
+    kernel with the identity resize.  The merged sample carries ``pred_sem_seg`` (uint8 1 x H x W, as ``predict``),
+    ``gt_sem_seg`` / ``img_path`` of the first view, and -- a deviation: the reference leaves the LAST VIEW's logits
+    there -- the mean probabilities in ``seg_logits``."""
+
+    def __init__(self, module):
+        super().__init__()
+        self.module = MODELS.build(module) if isinstance(module, dict) else module
+        if self.module.out_channels == 1:
+            raise NotImplementedError('binary (sigmoid / threshold) heads are not used by the LED-Net config')
+
+    @staticmethod
+    def _finish(last, first, probs, mask):
+        last.seg_logits = PixelData(data=probs)
+        last.pred_sem_seg = PixelData(data=mask[None])
+        if hasattr(first, 'gt_sem_seg'):
+            last.gt_sem_seg = first.gt_sem_seg
+        if 'img_path' in first.metainfo:
+            last.metainfo['img_path'] = first.metainfo['img_path']
+        return last
+
+    def merge_preds(self, data_samples_list):
+        """data_samples_list: per image, the predicted samples of its views (``seg_logits.data`` C x H x W at the
+        original size) -> one merged sample per image (seg_tta.py:15-47)"""
+        predictions = []
+        for data_samples in data_samples_list:
+            K = len(data_samples)
+            first = data_samples[0].seg_logits.data
+            acc = torch.empty(tuple(first.shape), dtype=torch.float32, device=first.device)
+            mask = torch.empty(tuple(first.shape[1:]), dtype=torch.uint8, device=first.device)
+            for k, ds in enumerate(data_samples):
+                lg = ds.seg_logits.data
+                if tuple(lg.shape) != tuple(first.shape):
+                    raise ops.LednError(f'merge_preds: view {k} has logits {tuple(lg.shape)}, view 0 {tuple(first.shape)}')
+                ops.tta_accumulate(lg.float().contiguous(), acc, first=k == 0, last=k == K - 1, K=K, planar=True,
+                                   mask=mask if k == K - 1 else None)
+            predictions.append(self._finish(data_samples[-1], data_samples[0], acc, mask))
+        return predictions
+
+    def test_step(self, data):
+        """data: every value is a list over the views of per-view batches (``inputs[v]``: the N images of view v,
+        ``data_samples[v]``: their samples) -> N merged samples"""
+        m = self.module
+        views_in, views_ds = data['inputs'], data['data_samples']
+        K = len(views_in)
+        assert K > 0 and len(views_ds) == K
+        accs = masks = None
+        with torch.no_grad():
+            for k in range(K):
+                d = m.data_preprocessor(dict(inputs=views_in[k], data_samples=views_ds[k]), False)
+                batch, samples = d['inputs'], d['data_samples']
+                N, _, H, W = batch.shape
+                slide = m.test_cfg.get('mode', 'whole') == 'slide'
+                if slide:
+                    logits = m.inference(batch, [ds.metainfo for ds in samples])          # planar N x C x H x W
+                else:
+                    assert m.test_cfg.get('mode', 'whole') == 'whole'
+                    logits = m.decode_head.predict_nhwc(m.extract_feat(batch, samples))     # N x H x W x C
+                if accs is None:
+                    sizes = [tuple(ds.metainfo.get('ori_shape', (H, W))[:2]) for ds in samples]
+                    accs = [torch.empty((m.out_channels,) + sz, dtype=torch.float32, device=batch.device) for sz in sizes]
+                    masks = [torch.empty(sz, dtype=torch.uint8, device=batch.device) for sz in sizes]
+                assert len(samples) == len(accs), 'every view must hold the same images'
+                for i, ds in enumerate(samples):
+                    left, right, top, bottom = m._padding(ds)
+                    if left or top:
+                        raise NotImplementedError('stack_batch pads right/bottom only (misc.py:83,87)')
+                    ops.tta_accumulate(logits[i], accs[i], first=k == 0, last=k == K - 1, K=K,
+                                       valid=(H - bottom, W - right), planar=slide,
+                                       flip=ds.metainfo.get('flip_direction') if ds.metainfo.get('flip') else None,
+                                       mask=masks[i] if k == K - 1 else None)
+        return [self._finish(views_ds[-1][i], views_ds[0][i], accs[i], masks[i]) for i in range(len(accs))]
+
+    def forward(self, inputs, data_samples=None, mode='tensor'):
+        return self.module(inputs, data_samples, mode)

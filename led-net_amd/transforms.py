@@ -342,3 +342,47 @@ class Compose:
                                         metainfo=dict(meta, img_shape=(p.ch, p.cw), pad_shape=(OH, OW),
                                                       padding_size=(0, OW - p.cw, 0, OH - p.ch))))
         return dict(inputs=inputs, data_samples=data_samples, batch=batch, labels=labels, padded_samples=padded)
+
+
+@register
+class TestTimeAug:
+    """mmcv's TestTimeAug: ``transforms=[[a1, a2, ...], [b1, b2], ...]`` -> one view per element of the cartesian
+    product a x b x ... (the first list varies slowest: scale-major, flip-minor for the cityscapes ``tta_pipeline``),
+    each view the sub-pipeline ``[a_i, b_j, ...]`` applied to a copy of the sample.
+
+    ``transform(dict(img=uint8 H x W x 3 device tensor, gt_seg_map=uint8 H x W (optional), ...))`` ->
+    ``dict(inputs=[3 x h x w uint8 per view], data_samples=[SegDataSample per view])``: one packed list per key.  As in
+    the reference's pipeline, where LoadAnnotations follows the geometric transforms, the label map is NOT resized or
+    flipped: every view's sample carries it at the original size.  One ``ledn_augment_batch`` launch per view."""
+    __test__ = False        # (not a pytest class)
+
+    def __init__(self, transforms, pad_val=0, seg_pad_val=255):
+        import itertools
+        assert transforms and all(isinstance(t, (list, tuple)) and len(t) > 0 for t in transforms), \
+            'transforms: a list of non-empty lists of transform configs'
+        self.views = [Compose(list(combo), pad_val, seg_pad_val) for combo in itertools.product(*transforms)]
+
+    def __len__(self):
+        return len(self.views)
+
+    def transform(self, results):
+        gt = results.get('gt_seg_map')
+        inputs, samples = [], []
+        for view in self.views:
+            r = {k: v for k, v in results.items() if k not in ('gt_seg_map', '_aug')}
+            out = view.batch([r])
+            ds = out['data_samples'][0]
+            if gt is not None:
+                ds.gt_sem_seg = PixelData(data=gt[None].long())
+            inputs.append(out['inputs'][0])
+            samples.append(ds)
+        return dict(inputs=inputs, data_samples=samples)
+
+
+def collate_views(packed):
+    """[TestTimeAug result per image] -> the layout ``SegTTAModel.test_step`` takes: every value a list over the
+    views of per-view batches"""
+    K = len(packed[0]['inputs'])
+    assert all(len(p['inputs']) == K for p in packed)
+    return dict(inputs=[[p['inputs'][k] for p in packed] for k in range(K)],
+                data_samples=[[p['data_samples'][k] for p in packed] for k in range(K)])
