@@ -757,6 +757,38 @@ int ledn_ohem2_up_bwd(const float* src0, const float* src1, int N, int Hs, int W
                       const float* work, const float* out, const float* dloss0, const float* dloss1,
                       float loss_weight0, float loss_weight1, float* dsrc0, float* dsrc1, void* stream);
 long long ledn_ohem2_work_floats(long long P);
+/* The three losses above with OhemCrossEntropy's class_weight (ohem_cross_entropy_loss.py:42,62-90: the per-pixel
+ * losses come from F.cross_entropy(weight=class_weight, reduction='none'), selection and .mean() are as before).
+ * class_weight: [C] f32 on the device (C = 2 for the resize-folded forms; class_weight0 / class_weight1 for the two
+ * losses of the pair); a NULL pointer means unweighted, and with every weight pointer NULL a call is exactly its
+ * unweighted twin above (same kernels, same results).  With w = class_weight and y_p the label of pixel p:
+ *   per-pixel loss          w[y_p] * CE_p
+ *   selection               unchanged: target-class probability, k-th order statistic, thr = max(kth, thres), strict <
+ *                           (out[2], out[3] and the accuracy out[1] do not depend on w)
+ *   out[0]                  loss_weight * sum_selected(w[y_p] * CE_p) / #selected   -- the COUNT of selected pixels, not
+ *                           the sum of their weights; 0 if no valid pixel
+ *   dlogits[p][c]           dloss * loss_weight * w[y_p] / #selected * (softmax_c - onehot_c) on selected pixels, else 0
+ * work sizes and layouts, out and every other argument are those of the unweighted entry points. */
+int ledn_ohem_ce_w_fwd(const float* logits, const long long* target, long long P, int C, float thres,
+                       long long min_kept, float loss_weight, int ignore_label, const float* class_weight,
+                       float* work, float* out, void* stream);
+int ledn_ohem_ce_w_bwd(const float* logits, const long long* target, long long P, int C, int ignore_label,
+                       const float* work, const float* out, const float* dloss, float loss_weight,
+                       const float* class_weight, float* dlogits, void* stream);
+int ledn_ohem_ce_up_w_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target, float thres,
+                          long long min_kept, float loss_weight, int ignore_label, const float* class_weight,
+                          float* work, float* out, void* stream);
+int ledn_ohem_ce_up_w_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                          int ignore_label, const float* work, const float* out, const float* dloss, float loss_weight,
+                          const float* class_weight, float* dsrc, void* stream);
+int ledn_ohem2_up_w_fwd(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W,
+                        const long long* target, float thres0, long long min_kept0, float loss_weight0, float thres1,
+                        long long min_kept1, float loss_weight1, int ignore_label, const float* class_weight0,
+                        const float* class_weight1, float* work, float* out, void* stream);
+int ledn_ohem2_up_w_bwd(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W, int ignore_label,
+                        const float* work, const float* out, const float* dloss0, const float* dloss1,
+                        float loss_weight0, float loss_weight1, const float* class_weight0, const float* class_weight1,
+                        float* dsrc0, float* dsrc1, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * The four pooled-context MLPs of Muti_AFF (classification/model_utils.py:377-400: AdaptiveAvgPool2d(S) ->

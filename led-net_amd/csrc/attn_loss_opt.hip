@@ -449,6 +449,10 @@ int window_attn_bwd_impl(const void* qkv, const float* biasT, const void* dout, 
 // work layout (floats): prob[P] | loss[P] | u32 hist[3][2048] | u32 state[16]
 // state: 0 n_valid, 1 n_correct, 2 rank (remaining), 3 prefix bits, 4 thr bits,
 //        5 n_selected, 6 (float) loss_sum
+// class_weight (the WT = true instances, cw = [C] floats on the device): loss[p] = cw[y_p] * CE_p in the probability
+// pass and the gradient coefficient times cw[y_p] in the backward; prob[], the histograms, the k-th order statistic and
+// the masked mean's COUNT never see the weights (ohem_cross_entropy_loss.py:62-90: selection on the probabilities,
+// .mean() of the reduction='none' losses).  The WT = false instances are the unweighted code, cw unused.
 // ===========================================================================
 constexpr int OH_BINS = 2048;
 struct OhemWork {
@@ -472,9 +476,9 @@ __device__ __forceinline__ int oh_bin(unsigned u, int pass) {
 }
 
 // pass over the pixels: prob of the target class, CE, validity, accuracy, level-0 histogram
-template <int CT>
+template <int CT, bool WT>
 __global__ void __launch_bounds__(256) ohem_prob_kernel(const float* logits, const long long* target, long P,
-                                                        int C, int ignore_label, float* work) {
+                                                        int C, int ignore_label, float* work, const float* cw) {
     __shared__ unsigned s_hist[OH_BINS];
     __shared__ unsigned s_cnt[2];
     const OhemWork w = ohem_work(work, P);
@@ -502,7 +506,8 @@ __global__ void __launch_bounds__(256) ohem_prob_kernel(const float* logits, con
         const float lt = lg[(int)tg] - mx;
         const float pr = __expf(lt) / se;
         w.prob[p] = pr;
-        w.loss[p] = __logf(se) - lt;
+        if constexpr (WT) w.loss[p] = cw[(int)tg] * (__logf(se) - lt);
+        else w.loss[p] = __logf(se) - lt;
         atomicAdd(&s_hist[oh_bin(__float_as_uint(pr), 0)], 1u);
         atomicAdd(&s_cnt[0], 1u);
         if (am == (int)tg) atomicAdd(&s_cnt[1], 1u);
@@ -644,15 +649,20 @@ __global__ void ohem_final_kernel(float* work, long P, float loss_weight, float*
 }
 
 int ohem_ce_fwd_impl(const float* logits, const long long* target, long long P, int C, float thres,
-                     long long min_kept, float loss_weight, int ignore_label, float* work, float* out,
-                     hipStream_t s) {
+                     long long min_kept, float loss_weight, int ignore_label, const float* cw, float* work,
+                     float* out, hipStream_t s) {
     LEDN_REQUIRE(logits && target && work && out && P > 0 && C > 1 && min_kept >= 1);
     LEDN_REQUIRE(P < (1LL << 31));
     const OhemWork w = ohem_work(work, P);
     if (hipMemsetAsync(w.hist, 0, sizeof(unsigned) * (3 * OH_BINS + 16), s) != hipSuccess) return LEDN_ELAUNCH;
     const dim3 grid((unsigned)(cdiv(P, 256) < 2048 ? cdiv(P, 256) : 2048));
-    if (C == 2) LEDN_LAUNCH(ohem_prob_kernel<2>, grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work);
-    else LEDN_LAUNCH(ohem_prob_kernel<0>, grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work);
+    if (cw) {
+        if (C == 2) LEDN_LAUNCH((ohem_prob_kernel<2, true>), grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work, cw);
+        else LEDN_LAUNCH((ohem_prob_kernel<0, true>), grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work, cw);
+    } else {
+        if (C == 2) LEDN_LAUNCH((ohem_prob_kernel<2, false>), grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work, cw);
+        else LEDN_LAUNCH((ohem_prob_kernel<0, false>), grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work, cw);
+    }
     LEDN_LAUNCH(ohem_scan_kernel, dim3(1), dim3(256), 0, s, work, (long)P, 0, min_kept, thres);
     LEDN_LAUNCH(ohem_hist_kernel, grid, dim3(256), 0, s, work, (long)P, 1);
     LEDN_LAUNCH(ohem_scan_kernel, dim3(1), dim3(256), 0, s, work, (long)P, 1, min_kept, thres);
@@ -663,11 +673,11 @@ int ohem_ce_fwd_impl(const float* logits, const long long* target, long long P, 
     return check_launch();
 }
 
-template <int CT>
+template <int CT, bool WT>
 __global__ void __launch_bounds__(256) ohem_bwd_kernel(const float* logits, const long long* target, long P,
                                                        int C, int ignore_label, const float* work,
                                                        const float* out, const float* dloss,
-                                                       float loss_weight, float* dlogits) {
+                                                       float loss_weight, float* dlogits, const float* cw) {
     const float* prob = work;
     const float thr = out[2];
     const float coef = dloss[0] * loss_weight / out[3];
@@ -689,23 +699,31 @@ __global__ void __launch_bounds__(256) ohem_bwd_kernel(const float* logits, cons
 #pragma unroll
         for (int c = 0; c < cc; ++c) se += __expf(lg[c] - mx);
         const float inv = 1.f / se;
+        const float cf = WT ? coef * cw[(int)tg] : coef;
 #pragma unroll
         for (int c = 0; c < cc; ++c)
-            dl[c] = coef * (__expf(lg[c] - mx) * inv - (c == (int)tg ? 1.f : 0.f));
+            dl[c] = cf * (__expf(lg[c] - mx) * inv - (c == (int)tg ? 1.f : 0.f));
     }
 }
 
 int ohem_ce_bwd_impl(const float* logits, const long long* target, long long P, int C, int ignore_label,
                      const float* work, const float* out, const float* dloss, float loss_weight,
-                     float* dlogits, hipStream_t s) {
+                     const float* cw, float* dlogits, hipStream_t s) {
     LEDN_REQUIRE(logits && target && work && out && dloss && dlogits && P > 0 && C > 1);
     const dim3 grid((unsigned)(cdiv(P, 256) < 4096 ? cdiv(P, 256) : 4096));
-    if (C == 2)
-        LEDN_LAUNCH(ohem_bwd_kernel<2>, grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work,
-                    out, dloss, loss_weight, dlogits);
+    if (cw) {
+        if (C == 2)
+            LEDN_LAUNCH((ohem_bwd_kernel<2, true>), grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work,
+                        out, dloss, loss_weight, dlogits, cw);
+        else
+            LEDN_LAUNCH((ohem_bwd_kernel<0, true>), grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work,
+                        out, dloss, loss_weight, dlogits, cw);
+    } else if (C == 2)
+        LEDN_LAUNCH((ohem_bwd_kernel<2, false>), grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work,
+                    out, dloss, loss_weight, dlogits, cw);
     else
-        LEDN_LAUNCH(ohem_bwd_kernel<0>, grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work,
-                    out, dloss, loss_weight, dlogits);
+        LEDN_LAUNCH((ohem_bwd_kernel<0, false>), grid, dim3(256), 0, s, logits, target, (long)P, C, ignore_label, work,
+                    out, dloss, loss_weight, dlogits, cw);
     return check_launch();
 }
 
@@ -727,8 +745,10 @@ __device__ __forceinline__ void up_logits2(const float* src, int Ws, const Lerp&
     l1 = ly.w0 * (lx.w0 * v00.y + lx.w1 * v01.y) + ly.w1 * (lx.w0 * v10.y + lx.w1 * v11.y);
 }
 
+template <bool WT>
 __global__ void __launch_bounds__(256) ohem_prob_up_kernel(const float* src, int N, int Hs, int Ws, int H, int W,
-                                                           const long long* target, int ignore_label, float* work) {
+                                                           const long long* target, int ignore_label, float* work,
+                                                           const float* cw) {
     __shared__ unsigned s_hist[OH_BINS];
     __shared__ unsigned s_cnt[2];
     const long P = (long)N * H * W;
@@ -753,7 +773,8 @@ __global__ void __launch_bounds__(256) ohem_prob_up_kernel(const float* src, int
         const float lt = lg[(int)tg] - mx;
         const float pr = __expf(lt) / se;
         w.prob[p] = pr;
-        w.loss[p] = __logf(se) - lt;
+        if constexpr (WT) w.loss[p] = cw[(int)tg] * (__logf(se) - lt);
+        else w.loss[p] = __logf(se) - lt;
         atomicAdd(&s_hist[oh_bin(__float_as_uint(pr), 0)], 1u);
         atomicAdd(&s_cnt[0], 1u);
         if (am == (int)tg) atomicAdd(&s_cnt[1], 1u);
@@ -765,15 +786,16 @@ __global__ void __launch_bounds__(256) ohem_prob_up_kernel(const float* src, int
 }
 
 int ohem_ce_up_fwd_impl(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target, float thres,
-                        long long min_kept, float loss_weight, int ignore_label, float* work, float* out,
-                        hipStream_t s) {
+                        long long min_kept, float loss_weight, int ignore_label, const float* cw, float* work,
+                        float* out, hipStream_t s) {
     LEDN_REQUIRE(src && target && work && out && N > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0);
     const long long P = (long long)N * H * W;
     LEDN_REQUIRE(P < (1LL << 31) && min_kept >= 1);
     const OhemWork w = ohem_work(work, P);
     if (hipMemsetAsync(w.hist, 0, sizeof(unsigned) * (3 * OH_BINS + 16), s) != hipSuccess) return LEDN_ELAUNCH;
     const dim3 grid((unsigned)(cdiv(P, 256) < 2048 ? cdiv(P, 256) : 2048));
-    LEDN_LAUNCH(ohem_prob_up_kernel, grid, dim3(256), 0, s, src, N, Hs, Ws, H, W, target, ignore_label, work);
+    if (cw) LEDN_LAUNCH(ohem_prob_up_kernel<true>, grid, dim3(256), 0, s, src, N, Hs, Ws, H, W, target, ignore_label, work, cw);
+    else LEDN_LAUNCH(ohem_prob_up_kernel<false>, grid, dim3(256), 0, s, src, N, Hs, Ws, H, W, target, ignore_label, work, cw);
     LEDN_LAUNCH(ohem_scan_kernel, dim3(1), dim3(256), 0, s, work, (long)P, 0, min_kept, thres);
     LEDN_LAUNCH(ohem_hist_kernel, grid, dim3(256), 0, s, work, (long)P, 1);
     LEDN_LAUNCH(ohem_scan_kernel, dim3(1), dim3(256), 0, s, work, (long)P, 1, min_kept, thres);
@@ -784,10 +806,11 @@ int ohem_ce_up_fwd_impl(const float* src, int N, int Hs, int Ws, int H, int W, c
     return check_launch();
 }
 
+template <bool WT>
 __global__ void __launch_bounds__(256) ohem_bwd_up2_kernel(const float* src, int N, int Hs, int Ws,
                                                            const long long* target, int ignore_label,
                                                            const float* work, const float* out, const float* dloss,
-                                                           float loss_weight, float* dsrc) {
+                                                           float loss_weight, float* dsrc, const float* cw) {
     constexpr int T = 16, CH = 2 * T + 2;                   // src tile, children per side
     __shared__ float2 s_g[CH * CH];
     const int H = 2 * Hs, W = 2 * Ws;
@@ -809,8 +832,9 @@ __global__ void __launch_bounds__(256) ohem_bwd_up2_kernel(const float* src, int
                 up_logits2(sn, Ws, lerp_coord(y, Hs, H), lerp_coord(x, Ws, W), l0, l1);
                 const float mx = fmaxf(l0, l1);
                 const float e0 = __expf(l0 - mx), e1 = __expf(l1 - mx), inv = 1.f / (e0 + e1);
-                g.x = coef * (e0 * inv - (tg == 0 ? 1.f : 0.f));
-                g.y = coef * (e1 * inv - (tg == 1 ? 1.f : 0.f));
+                const float cf = WT ? coef * cw[(int)tg] : coef;
+                g.x = cf * (e0 * inv - (tg == 0 ? 1.f : 0.f));
+                g.y = cf * (e1 * inv - (tg == 1 ? 1.f : 0.f));
             }
         }
         s_g[k] = g;
@@ -841,13 +865,17 @@ __global__ void __launch_bounds__(256) ohem_bwd_up2_kernel(const float* src, int
 
 int ohem_ce_up_bwd_impl(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
                         int ignore_label, const float* work, const float* out, const float* dloss, float loss_weight,
-                        float* dsrc, hipStream_t s) {
+                        const float* cw, float* dsrc, hipStream_t s) {
     LEDN_REQUIRE(src && target && work && out && dloss && dsrc && N > 0 && Hs > 0 && Ws > 0);
     LEDN_REQUIRE(H == 2 * Hs && W == 2 * Ws);               // the fused adjoint is written for the exact 2x resize
     const long nb = (long)N * cdiv(Hs, 16) * cdiv(Ws, 16);
     LEDN_REQUIRE(nb < (1L << 31));
-    LEDN_LAUNCH(ohem_bwd_up2_kernel, dim3((unsigned)nb), dim3(256), 0, s, src, N, Hs, Ws, target, ignore_label, work, out,
-                dloss, loss_weight, dsrc);
+    if (cw)
+        LEDN_LAUNCH(ohem_bwd_up2_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, src, N, Hs, Ws, target, ignore_label, work,
+                    out, dloss, loss_weight, dsrc, cw);
+    else
+        LEDN_LAUNCH(ohem_bwd_up2_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, src, N, Hs, Ws, target, ignore_label, work,
+                    out, dloss, loss_weight, dsrc, cw);
     return check_launch();
 }
 

@@ -106,25 +106,27 @@ int mfaf_gate_bwd_impl(const ledn_mfafbwd_desc& d, hipStream_t s);
 int mfaf_bwd_combine_impl(void* dx, void* dr, const void* dxl, const float* const* dpool, const int* sizes,
                           int npool, int N, int H, int W, int C, int dtype, hipStream_t s);
 long long ohem_work_floats(long long P);
+// (cw / cw0 / cw1: class weights on the device, null = unweighted)
 int ohem_ce_fwd_impl(const float* logits, const long long* target, long long P, int C, float thres,
-                     long long min_kept, float loss_weight, int ignore_label, float* work, float* out,
-                     hipStream_t s);
+                     long long min_kept, float loss_weight, int ignore_label, const float* cw, float* work,
+                     float* out, hipStream_t s);
 int ohem_ce_up_fwd_impl(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target, float thres,
-                        long long min_kept, float loss_weight, int ignore_label, float* work, float* out,
-                        hipStream_t s);
+                        long long min_kept, float loss_weight, int ignore_label, const float* cw, float* work,
+                        float* out, hipStream_t s);
 int ohem2_up_fwd_impl(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W,
                       const long long* target, float thres0, long long min_kept0, float lw0, float thres1,
-                      long long min_kept1, float lw1, int ignore_label, float* work, float* out, hipStream_t s);
+                      long long min_kept1, float lw1, int ignore_label, const float* cw0, const float* cw1,
+                      float* work, float* out, hipStream_t s);
 int ohem2_up_bwd_impl(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W, int ignore_label,
                       const float* work, const float* out, const float* dloss0, const float* dloss1, float lw0,
-                      float lw1, float* dsrc0, float* dsrc1, hipStream_t s);
+                      float lw1, const float* cw0, const float* cw1, float* dsrc0, float* dsrc1, hipStream_t s);
 long long ohem2_work_floats(long long P);
 int ohem_ce_up_bwd_impl(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
                         int ignore_label, const float* work, const float* out, const float* dloss, float loss_weight,
-                        float* dsrc, hipStream_t s);
+                        const float* cw, float* dsrc, hipStream_t s);
 int ohem_ce_bwd_impl(const float* logits, const long long* target, long long P, int C, int ignore_label,
                      const float* work, const float* out, const float* dloss, float loss_weight,
-                     float* dlogits, hipStream_t s);
+                     const float* cw, float* dlogits, hipStream_t s);
 int tta_accumulate_impl(const ledn_tta_desc& d, hipStream_t s);
 int slide_accumulate_impl(float* canvas, const float* crop, int N, int C, int H, int W, int y1, int x1, int hc, int wc,
                           int crop_planar, hipStream_t s);
@@ -509,35 +511,73 @@ long long ledn_ohem_work_floats(long long P) { return ohem_work_floats(P); }
 int ledn_ohem_ce_fwd(const float* logits, const long long* target, long long P, int C, float thres,
                      long long min_kept, float loss_weight, int ignore_label, float* work, float* out,
                      void* stream) {
-    return ohem_ce_fwd_impl(logits, target, P, C, thres, min_kept, loss_weight, ignore_label, work, out,
+    return ohem_ce_fwd_impl(logits, target, P, C, thres, min_kept, loss_weight, ignore_label, nullptr, work, out,
+                            S(stream));
+}
+int ledn_ohem_ce_w_fwd(const float* logits, const long long* target, long long P, int C, float thres,
+                       long long min_kept, float loss_weight, int ignore_label, const float* class_weight,
+                       float* work, float* out, void* stream) {
+    return ohem_ce_fwd_impl(logits, target, P, C, thres, min_kept, loss_weight, ignore_label, class_weight, work, out,
                             S(stream));
 }
 int ledn_ohem_ce_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target, float thres,
                         long long min_kept, float loss_weight, int ignore_label, float* work, float* out, void* stream) {
-    return ohem_ce_up_fwd_impl(src, N, Hs, Ws, H, W, target, thres, min_kept, loss_weight, ignore_label, work, out, S(stream));
+    return ohem_ce_up_fwd_impl(src, N, Hs, Ws, H, W, target, thres, min_kept, loss_weight, ignore_label, nullptr, work, out, S(stream));
+}
+int ledn_ohem_ce_up_w_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target, float thres,
+                          long long min_kept, float loss_weight, int ignore_label, const float* class_weight,
+                          float* work, float* out, void* stream) {
+    return ohem_ce_up_fwd_impl(src, N, Hs, Ws, H, W, target, thres, min_kept, loss_weight, ignore_label, class_weight, work,
+                               out, S(stream));
 }
 int ledn_ohem2_up_fwd(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W,
                       const long long* target, float thres0, long long min_kept0, float loss_weight0, float thres1,
                       long long min_kept1, float loss_weight1, int ignore_label, float* work, float* out, void* stream) {
     return ohem2_up_fwd_impl(src0, src1, N, Hs, Ws, H, W, target, thres0, min_kept0, loss_weight0, thres1, min_kept1,
-                             loss_weight1, ignore_label, work, out, S(stream));
+                             loss_weight1, ignore_label, nullptr, nullptr, work, out, S(stream));
+}
+int ledn_ohem2_up_w_fwd(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W,
+                        const long long* target, float thres0, long long min_kept0, float loss_weight0, float thres1,
+                        long long min_kept1, float loss_weight1, int ignore_label, const float* class_weight0,
+                        const float* class_weight1, float* work, float* out, void* stream) {
+    return ohem2_up_fwd_impl(src0, src1, N, Hs, Ws, H, W, target, thres0, min_kept0, loss_weight0, thres1, min_kept1,
+                             loss_weight1, ignore_label, class_weight0, class_weight1, work, out, S(stream));
 }
 int ledn_ohem2_up_bwd(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W, int ignore_label,
                       const float* work, const float* out, const float* dloss0, const float* dloss1,
                       float loss_weight0, float loss_weight1, float* dsrc0, float* dsrc1, void* stream) {
     return ohem2_up_bwd_impl(src0, src1, N, Hs, Ws, H, W, ignore_label, work, out, dloss0, dloss1, loss_weight0,
-                             loss_weight1, dsrc0, dsrc1, S(stream));
+                             loss_weight1, nullptr, nullptr, dsrc0, dsrc1, S(stream));
+}
+int ledn_ohem2_up_w_bwd(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W, int ignore_label,
+                        const float* work, const float* out, const float* dloss0, const float* dloss1,
+                        float loss_weight0, float loss_weight1, const float* class_weight0, const float* class_weight1,
+                        float* dsrc0, float* dsrc1, void* stream) {
+    return ohem2_up_bwd_impl(src0, src1, N, Hs, Ws, H, W, ignore_label, work, out, dloss0, dloss1, loss_weight0,
+                             loss_weight1, class_weight0, class_weight1, dsrc0, dsrc1, S(stream));
 }
 long long ledn_ohem2_work_floats(long long P) { return ohem2_work_floats(P); }
 int ledn_ohem_ce_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
                         int ignore_label, const float* work, const float* out, const float* dloss, float loss_weight,
                         float* dsrc, void* stream) {
-    return ohem_ce_up_bwd_impl(src, N, Hs, Ws, H, W, target, ignore_label, work, out, dloss, loss_weight, dsrc, S(stream));
+    return ohem_ce_up_bwd_impl(src, N, Hs, Ws, H, W, target, ignore_label, work, out, dloss, loss_weight, nullptr, dsrc, S(stream));
+}
+int ledn_ohem_ce_up_w_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                          int ignore_label, const float* work, const float* out, const float* dloss, float loss_weight,
+                          const float* class_weight, float* dsrc, void* stream) {
+    return ohem_ce_up_bwd_impl(src, N, Hs, Ws, H, W, target, ignore_label, work, out, dloss, loss_weight, class_weight, dsrc,
+                               S(stream));
 }
 int ledn_ohem_ce_bwd(const float* logits, const long long* target, long long P, int C, int ignore_label,
                      const float* work, const float* out, const float* dloss, float loss_weight,
                      float* dlogits, void* stream) {
-    return ohem_ce_bwd_impl(logits, target, P, C, ignore_label, work, out, dloss, loss_weight, dlogits,
+    return ohem_ce_bwd_impl(logits, target, P, C, ignore_label, work, out, dloss, loss_weight, nullptr, dlogits,
+                            S(stream));
+}
+int ledn_ohem_ce_w_bwd(const float* logits, const long long* target, long long P, int C, int ignore_label,
+                       const float* work, const float* out, const float* dloss, float loss_weight,
+                       const float* class_weight, float* dlogits, void* stream) {
+    return ohem_ce_bwd_impl(logits, target, P, C, ignore_label, work, out, dloss, loss_weight, class_weight, dlogits,
                             S(stream));
 }
 int ledn_sgd_step(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,

@@ -19,6 +19,10 @@
 //   * the three radix-select levels, the masked mean and the final scalars handle both losses per launch.
 // Selection semantics are exactly ohem_cross_entropy_loss.py:62-90 (k-th order statistic over the valid pixels,
 // threshold = max(k-th, thres), strict <), bit-exact as the single-loss kernels.
+// class_weight (two floats per loss on the device, either pointer may be null = that loss unweighted): only the masked
+// mean and the backward see it (their WT = true instances).  The masked mean reads the uint8 label plane next to the
+// stored probabilities and sums -w[y] log p, still dividing by the COUNT of selected pixels; the backward, which reads
+// that plane anyway, scales coef_k by w_k[y].  Probabilities, histograms, scans and thresholds are the unweighted ones.
 //
 // work layout (floats): prob0[P] | prob1[P] | lab8[P bytes, padded to 16 B] | u32 hist[2][3][O2_REP][2048] |
 //                       u32 cnt[O2_REP][2] (n_valid, n_correct) | float part[O2_GRID][4] | u32 state[2][16]
@@ -328,16 +332,25 @@ __global__ void __launch_bounds__(256) ohem2_hist_kernel(float* work, long P, in
     }
 }
 
-// masked mean: sum of -log p over p < threshold, and the count, for both losses
-__global__ void __launch_bounds__(256) ohem2_reduce_kernel(float* work, long P) {
+// masked mean: sum of -log p (WT: -w[label] log p, the weights of both classes held in registers) over p < threshold,
+// and the count, for both losses
+template <bool WT>
+__global__ void __launch_bounds__(256) ohem2_reduce_kernel(float* work, long P, const float* cw0, const float* cw1) {
     __shared__ float s_sum[2][4];
     __shared__ unsigned s_cnt[2][4];
     const Ohem2Work w = o2_work(work, P);
     const float thr[2] = {__uint_as_float(w.state[4]), __uint_as_float(w.state[16 + 4])};
     float sum[2] = {0.f, 0.f};
     unsigned cnt[2] = {0u, 0u};
+    float wt[2][2] = {{1.f, 1.f}, {1.f, 1.f}};          // [loss][class]
+    if constexpr (WT) {
+        if (cw0) { wt[0][0] = cw0[0]; wt[0][1] = cw0[1]; }
+        if (cw1) { wt[1][0] = cw1[0]; wt[1][1] = cw1[1]; }
+    }
     const long nq = P / 4, stride = (long)gridDim.x * blockDim.x;
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += stride) {
+        unsigned lab = 0u;
+        if constexpr (WT) lab = *reinterpret_cast<const unsigned*>(w.lab8 + q * 4);      // four labels, one per byte
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const float4 v = *reinterpret_cast<const float4*>(w.prob[j] + q * 4);
@@ -345,7 +358,8 @@ __global__ void __launch_bounds__(256) ohem2_reduce_kernel(float* work, long P) 
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (pv[k] < thr[j]) {
-                    sum[j] -= __logf(pv[k]);
+                    if constexpr (WT) sum[j] -= (((lab >> (8 * k)) & 0xffu) == 1u ? wt[j][1] : wt[j][0]) * __logf(pv[k]);
+                    else sum[j] -= __logf(pv[k]);
                     ++cnt[j];
                 }
         }
@@ -406,7 +420,8 @@ __global__ void __launch_bounds__(256) ohem2_final_kernel(float* work, long P, i
 
 int ohem2_up_fwd_impl(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W,
                       const long long* target, float thres0, long long min_kept0, float lw0, float thres1,
-                      long long min_kept1, float lw1, int ignore_label, float* work, float* out, hipStream_t s) {
+                      long long min_kept1, float lw1, int ignore_label, const float* cw0, const float* cw1,
+                      float* work, float* out, hipStream_t s) {
     LEDN_REQUIRE(src0 && src1 && target && work && out && N > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0);
     LEDN_REQUIRE(W % 4 == 0 && ignore_label >= 0 && ignore_label <= 255);
     const long long P = (long long)N * H * W;
@@ -424,7 +439,8 @@ int ohem2_up_fwd_impl(const float* src0, const float* src1, int N, int Hs, int W
     LEDN_LAUNCH(ohem2_scan_kernel, dim3(2), dim3(256), 0, s, work, (long)P, 1, min_kept0, min_kept1, thres0, thres1);
     LEDN_LAUNCH(ohem2_hist_kernel, grid, dim3(256), 0, s, work, (long)P, 2);
     LEDN_LAUNCH(ohem2_scan_kernel, dim3(2), dim3(256), 0, s, work, (long)P, 2, min_kept0, min_kept1, thres0, thres1);
-    LEDN_LAUNCH(ohem2_reduce_kernel, grid, dim3(256), 0, s, work, (long)P);
+    if (cw0 || cw1) LEDN_LAUNCH(ohem2_reduce_kernel<true>, grid, dim3(256), 0, s, work, (long)P, cw0, cw1);
+    else LEDN_LAUNCH(ohem2_reduce_kernel<false>, grid, dim3(256), 0, s, work, (long)P, cw0, cw1);
     LEDN_LAUNCH(ohem2_final_kernel, dim3(1), dim3(256), 0, s, work, (long)P, (int)grid.x, lw0, lw1, out);
     return check_launch();
 }
@@ -432,11 +448,13 @@ int ohem2_up_fwd_impl(const float* src0, const float* src1, int N, int Hs, int W
 // Backward (exact 2x): a workgroup owns a 16 x 16 tile of the half-resolution maps; the softmax gradients of its
 // 34 x 34 children are formed once in LDS for BOTH losses (labels: the uint8 plane; selection: stored probability
 // < threshold; the gradient itself from the stored probability), then every source pixel gathers its 4 x 4 children
-// with the interpolation weights.  src0 / src1 are not read.
+// with the interpolation weights.  src0 / src1 are not read.  WT: coef_k times the class weight w_k[label].
+template <bool WT>
 __global__ void __launch_bounds__(512) ohem2_bwd_up2_kernel(const float* src0, const float* src1, int N, int Hs, int Ws,
                                                             int ignore_label, const float* work, const float* out,
                                                             const float* dloss0, const float* dloss1, float lw0,
-                                                            float lw1, float* dsrc0, float* dsrc1) {
+                                                            float lw1, float* dsrc0, float* dsrc1, const float* cw0,
+                                                            const float* cw1) {
     // 8 x 64 source pixels per workgroup: the 18 x 130 children are read as 520-byte row segments (the first version's
     // 16 x 16 tile read 136-byte segments at a 4 KB stride: two cache lines for 34 floats, 99 us at 2.2 TB/s)
     constexpr int TH = 8, TW = 64, CHH = 2 * TH + 2, CHW = 2 * TW + 2;
@@ -450,6 +468,11 @@ __global__ void __launch_bounds__(512) ohem2_bwd_up2_kernel(const float* src0, c
     const float thr0 = out[2], thr1 = out[4 + 2];
     const float coef0 = dloss0[0] * lw0 / out[3], coef1 = dloss1[0] * lw1 / out[4 + 3];
     (void)src0; (void)src1;
+    float wt[2][2] = {{1.f, 1.f}, {1.f, 1.f}};          // [loss][class]
+    if constexpr (WT) {
+        if (cw0) { wt[0][0] = cw0[0]; wt[0][1] = cw0[1]; }
+        if (cw1) { wt[1][0] = cw1[0]; wt[1][1] = cw1[1]; }
+    }
     const float sy = (float)Hs / (float)H, sx = (float)Ws / (float)W;
     for (int k = threadIdx.x; k < CHH * CHW; k += 512) {
         const int y = 2 * i0 - 1 + k / CHW, x = 2 * j0 - 1 + k % CHW;
@@ -463,12 +486,12 @@ __global__ void __launch_bounds__(512) ohem2_bwd_up2_kernel(const float* src0, c
                 // interpolation, no exponentials in the backward (the first version re-formed them: 143 us, VALU-bound)
                 const float p0 = w.prob[0][p], p1 = w.prob[1][p];
                 if (p0 < thr0) {
-                    const float d = coef0 * (1.f - p0);
+                    const float d = (WT ? coef0 * (tg == 1 ? wt[0][1] : wt[0][0]) : coef0) * (1.f - p0);
                     g.x = tg == 0 ? -d : d;
                     g.y = tg == 1 ? -d : d;
                 }
                 if (p1 < thr1) {
-                    const float d = coef1 * (1.f - p1);
+                    const float d = (WT ? coef1 * (tg == 1 ? wt[1][1] : wt[1][0]) : coef1) * (1.f - p1);
                     g.z = tg == 0 ? -d : d;
                     g.w = tg == 1 ? -d : d;
                 }
@@ -513,13 +536,17 @@ __global__ void __launch_bounds__(512) ohem2_bwd_up2_kernel(const float* src0, c
 
 int ohem2_up_bwd_impl(const float* src0, const float* src1, int N, int Hs, int Ws, int H, int W, int ignore_label,
                       const float* work, const float* out, const float* dloss0, const float* dloss1, float lw0,
-                      float lw1, float* dsrc0, float* dsrc1, hipStream_t s) {
+                      float lw1, const float* cw0, const float* cw1, float* dsrc0, float* dsrc1, hipStream_t s) {
     LEDN_REQUIRE(src0 && src1 && work && out && dloss0 && dloss1 && dsrc0 && dsrc1 && N > 0 && Hs > 0 && Ws > 0);
     LEDN_REQUIRE(H == 2 * Hs && W == 2 * Ws);               // the fused adjoint is written for the exact 2x resize
     const long nb = (long)N * cdiv(Hs, 8) * cdiv(Ws, 64);
     LEDN_REQUIRE(nb < (1L << 31));
-    LEDN_LAUNCH(ohem2_bwd_up2_kernel, dim3((unsigned)nb), dim3(512), 0, s, src0, src1, N, Hs, Ws, ignore_label, work,
-                out, dloss0, dloss1, lw0, lw1, dsrc0, dsrc1);
+    if (cw0 || cw1)
+        LEDN_LAUNCH(ohem2_bwd_up2_kernel<true>, dim3((unsigned)nb), dim3(512), 0, s, src0, src1, N, Hs, Ws, ignore_label, work,
+                    out, dloss0, dloss1, lw0, lw1, dsrc0, dsrc1, cw0, cw1);
+    else
+        LEDN_LAUNCH(ohem2_bwd_up2_kernel<false>, dim3((unsigned)nb), dim3(512), 0, s, src0, src1, N, Hs, Ws, ignore_label, work,
+                    out, dloss0, dloss1, lw0, lw1, dsrc0, dsrc1, cw0, cw1);
     return check_launch();
 }
 

@@ -437,8 +437,29 @@ def mfaf_bwd_combine(dx, dr, dxl, dpools):
     return dx, dr
 
 
-def ohem_ce_fwd(logits, target, thres, min_kept, loss_weight, ignore_label=255):
-    """logits [N,H,W,C] f32, target [N,H,W] int64 -> (out[4] = loss, acc, thr, nsel ; work)."""
+def _class_weight(cw, ref, Cc, who):
+    """OhemCrossEntropy's class_weight for the kernels: None, or a contiguous f32 vector of Cc finite values on ref's
+    device.  The values are read back once per tensor (and version); never inside a stream capture, where a
+    read-back is not allowed -- a weight that reaches a capture unchecked came from OhemCrossEntropy, which checked
+    the host list it was built from."""
+    if cw is None:
+        return None
+    if (not torch.is_tensor(cw) or cw.dtype != torch.float32 or cw.dim() != 1 or not cw.is_contiguous()
+            or cw.device != ref.device):
+        raise LednError(f'{who}: class_weight must be a contiguous float32 vector on the device of the logits')
+    if cw.numel() != Cc:
+        raise LednError(f'{who}: class_weight has {cw.numel()} entries, the logits have {Cc} classes')
+    if getattr(cw, '_ledn_finite', None) != cw._version:
+        if not (cw.is_cuda and torch.cuda.is_current_stream_capturing()):
+            if not bool(torch.isfinite(cw).all()):
+                raise LednError(f'{who}: class_weight must be finite')
+            cw._ledn_finite = cw._version
+    return cw
+
+
+def ohem_ce_fwd(logits, target, thres, min_kept, loss_weight, ignore_label=255, class_weight=None):
+    """logits [N,H,W,C] f32, target [N,H,W] int64 -> (out[4] = loss, acc, thr, nsel ; work).
+    class_weight: None or [C] f32 on the device -- per-pixel loss w[y] * CE, selection and the divisor unchanged."""
     lib = _lib.get_lib()
     if logits.dtype != torch.float32 or target.dtype != torch.int64:
         raise LednError('ohem_ce: logits f32 NHWC and int64 target required')
@@ -448,27 +469,39 @@ def ohem_ce_fwd(logits, target, thres, min_kept, loss_weight, ignore_label=255):
         raise LednError('ohem_ce: target shape')
     work = torch.empty(lib.cdll.ledn_ohem_work_floats(P), dtype=torch.float32, device=logits.device)
     out = torch.empty(4, dtype=torch.float32, device=logits.device)
+    cw = _class_weight(class_weight, logits, Cc, 'ohem_ce')
     _check(lib, logits, target, work, out)
+    if cw is not None:
+        _run(lib, 'ledn_ohem_ce_w_fwd', logits, _p(logits), _p(target), P, Cc, thres, int(min_kept), loss_weight,
+             ignore_label, _p(cw), _p(work), _p(out),
+             work=_ops._TIMING is not None and (f'ohem_w_fwd P{P} C{Cc}', _nb(logits, target) + 5 * 8 * P, 31 * P, 'ohem_prob_kernel'))
+        return out, work
     _run(lib, 'ledn_ohem_ce_fwd', logits, _p(logits), _p(target), P, Cc, thres, int(min_kept), loss_weight,
          ignore_label, _p(work), _p(out), work=_ops._TIMING is not None and (f'ohem_fwd P{P} C{Cc}', _nb(logits, target) + 5 * 8 * P, 30 * P))
     return out, work
 
 
-def ohem_ce_bwd(logits, target, work, out, dloss, loss_weight, ignore_label=255):
+def ohem_ce_bwd(logits, target, work, out, dloss, loss_weight, ignore_label=255, class_weight=None):
     lib = _lib.get_lib()
     Cc = logits.shape[-1]
     P = logits.numel() // Cc
     dl = torch.empty_like(logits)
     dloss = dloss.reshape(1).to(torch.float32).contiguous()
+    cw = _class_weight(class_weight, logits, Cc, 'ohem_ce_bwd')
     _check(lib, logits, target, work, out, dloss, dl)
+    if cw is not None:
+        _run(lib, 'ledn_ohem_ce_w_bwd', logits, _p(logits), _p(target), P, Cc, ignore_label, _p(work), _p(out),
+             _p(dloss), loss_weight, _p(cw), _p(dl),
+             work=_ops._TIMING is not None and (f'ohem_w_bwd P{P} C{Cc}', _nb(logits, target, dl) + 4 * P, 21 * P, 'ohem_bwd_kernel'))
+        return dl
     _run(lib, 'ledn_ohem_ce_bwd', logits, _p(logits), _p(target), P, Cc, ignore_label, _p(work), _p(out),
          _p(dloss), loss_weight, _p(dl), work=_ops._TIMING is not None and (f'ohem_bwd P{P} C{Cc}', _nb(logits, target, dl) + 4 * P, 20 * P))
     return dl
 
 
-def ohem_ce_up_fwd(src, target, thres, min_kept, loss_weight, ignore_label=255):
+def ohem_ce_up_fwd(src, target, thres, min_kept, loss_weight, ignore_label=255, class_weight=None):
     """OHEM-CE on bilinear(src -> target's H x W) without materialising the resized logits.
-    src [N,Hs,Ws,2] f32, target [N,H,W] int64 -> (out[4], work)."""
+    src [N,Hs,Ws,2] f32, target [N,H,W] int64 -> (out[4], work).  class_weight: None or [2] f32 on the device."""
     lib = _lib.get_lib()
     if src.dtype != torch.float32 or target.dtype != torch.int64 or src.dim() != 4 or src.shape[-1] != 2:
         raise LednError('ohem_ce_up: src f32 [N,Hs,Ws,2] and int64 target required')
@@ -479,14 +512,20 @@ def ohem_ce_up_fwd(src, target, thres, min_kept, loss_weight, ignore_label=255):
     P = N * H * W
     work = torch.empty(lib.cdll.ledn_ohem_work_floats(P), dtype=torch.float32, device=src.device)
     out = torch.empty(4, dtype=torch.float32, device=src.device)
+    cw = _class_weight(class_weight, src, 2, 'ohem_ce_up')
     _check(lib, src, target, work, out)
+    if cw is not None:
+        _run(lib, 'ledn_ohem_ce_up_w_fwd', src, _p(src), N, Hs, Ws, H, W, _p(target), thres, int(min_kept), loss_weight,
+             ignore_label, _p(cw), _p(work), _p(out),
+             work=_ops._TIMING is not None and (f'ohem_up_w_fwd P{P}', _nb(src, target) + 5 * 8 * P, 41 * P, 'ohem_prob_up_kernel'))
+        return out, work
     _run(lib, 'ledn_ohem_ce_up_fwd', src, _p(src), N, Hs, Ws, H, W, _p(target), thres, int(min_kept), loss_weight,
          ignore_label, _p(work), _p(out),
          work=_ops._TIMING is not None and (f'ohem_up_fwd P{P}', _nb(src, target) + 5 * 8 * P, 40 * P))
     return out, work
 
 
-def ohem_ce_up_bwd(src, target, work, out, dloss, loss_weight, ignore_label=255):
+def ohem_ce_up_bwd(src, target, work, out, dloss, loss_weight, ignore_label=255, class_weight=None):
     """-> dsrc [N,Hs,Ws,2]: the adjoint of the exact 2x resize applied to the loss gradient (never materialised)."""
     lib = _lib.get_lib()
     N, Hs, Ws, _ = src.shape
@@ -495,16 +534,24 @@ def ohem_ce_up_bwd(src, target, work, out, dloss, loss_weight, ignore_label=255)
         raise LednError('ohem_ce_up_bwd: exact 2x resize only')
     dsrc = torch.empty_like(src)
     dloss = dloss.reshape(1).to(torch.float32).contiguous()
+    cw = _class_weight(class_weight, src, 2, 'ohem_ce_up_bwd')
     _check(lib, src, target, work, out, dloss, dsrc)
+    if cw is not None:
+        _run(lib, 'ledn_ohem_ce_up_w_bwd', src, _p(src), N, Hs, Ws, H, W, _p(target), ignore_label, _p(work), _p(out),
+             _p(dloss), loss_weight, _p(cw), _p(dsrc),
+             work=_ops._TIMING is not None and (f'ohem_up_w_bwd P{N * H * W}', _nb(src, target, dsrc) + 4 * N * H * W, 31 * N * H * W,
+                                                'ohem_bwd_up2_kernel'))
+        return dsrc
     _run(lib, 'ledn_ohem_ce_up_bwd', src, _p(src), N, Hs, Ws, H, W, _p(target), ignore_label, _p(work), _p(out),
          _p(dloss), loss_weight, _p(dsrc),
          work=_ops._TIMING is not None and (f'ohem_up_bwd P{N * H * W}', _nb(src, target, dsrc) + 4 * N * H * W, 30 * N * H * W))
     return dsrc
 
 
-def ohem2_up_fwd(src0, src1, target, cfg0, cfg1, ignore_label=255):
+def ohem2_up_fwd(src0, src1, target, cfg0, cfg1, ignore_label=255, class_weights=(None, None)):
     """Both OHEM-CE losses of LEDHead.loss_by_feat in one launch set (ledn_ohem2_up_fwd).  src0 / src1 [N,Hs,Ws,2]
-    f32, target [N,H,W] int64, cfg_k = (thres, min_kept, loss_weight) -> (out [2,4], work)."""
+    f32, target [N,H,W] int64, cfg_k = (thres, min_kept, loss_weight) -> (out [2,4], work).
+    class_weights: per loss None or [2] f32 on the device (either may be None)."""
     lib = _lib.get_lib()
     for src in (src0, src1):
         if src.dtype != torch.float32 or src.dim() != 4 or src.shape[-1] != 2 or src.shape != src0.shape:
@@ -518,7 +565,14 @@ def ohem2_up_fwd(src0, src1, target, cfg0, cfg1, ignore_label=255):
     P = N * H * W
     work = torch.empty(lib.cdll.ledn_ohem2_work_floats(P), dtype=torch.float32, device=src0.device)
     out = torch.empty((2, 4), dtype=torch.float32, device=src0.device)
+    cw0, cw1 = (_class_weight(c, src0, 2, 'ohem2_up') for c in class_weights)
     _check(lib, src0, src1, target, work, out)
+    if cw0 is not None or cw1 is not None:
+        _run(lib, 'ledn_ohem2_up_w_fwd', src0, _p(src0), _p(src1), N, Hs, Ws, H, W, _p(target), cfg0[0], int(cfg0[1]), cfg0[2],
+             cfg1[0], int(cfg1[1]), cfg1[2], ignore_label, _p(cw0), _p(cw1), _p(work), _p(out),
+             work=_ops._TIMING is not None and (f'ohem2_up_w_fwd P{P}', _nb(src0, src1, target) + (2 + 5 * 8) * P, 82 * P,
+                                                'ohem2_prob_kernel'))
+        return out, work
     _run(lib, 'ledn_ohem2_up_fwd', src0, _p(src0), _p(src1), N, Hs, Ws, H, W, _p(target), cfg0[0], int(cfg0[1]), cfg0[2],
          cfg1[0], int(cfg1[1]), cfg1[2], ignore_label, _p(work), _p(out),
          work=_ops._TIMING is not None and (f'ohem2_up_fwd P{P}', _nb(src0, src1, target) + (1 + 5 * 8) * P, 80 * P,
@@ -526,7 +580,7 @@ def ohem2_up_fwd(src0, src1, target, cfg0, cfg1, ignore_label=255):
     return out, work
 
 
-def ohem2_up_bwd(src0, src1, hw, work, out, dloss0, dloss1, lw0, lw1, ignore_label=255):
+def ohem2_up_bwd(src0, src1, hw, work, out, dloss0, dloss1, lw0, lw1, ignore_label=255, class_weights=(None, None)):
     """-> (dsrc0, dsrc1): the adjoint of the exact 2x resize applied to both loss gradients (never materialised)."""
     lib = _lib.get_lib()
     N, Hs, Ws, _ = src0.shape
@@ -536,7 +590,14 @@ def ohem2_up_bwd(src0, src1, hw, work, out, dloss0, dloss1, lw0, lw1, ignore_lab
     d0, d1 = torch.empty_like(src0), torch.empty_like(src1)
     g0 = dloss0.reshape(1).to(torch.float32).contiguous()
     g1 = dloss1.reshape(1).to(torch.float32).contiguous()
+    cw0, cw1 = (_class_weight(c, src0, 2, 'ohem2_up_bwd') for c in class_weights)
     _check(lib, src0, src1, work, out, g0, g1, d0, d1)
+    if cw0 is not None or cw1 is not None:
+        _run(lib, 'ledn_ohem2_up_w_bwd', src0, _p(src0), _p(src1), N, Hs, Ws, H, W, ignore_label, _p(work), _p(out), _p(g0),
+             _p(g1), lw0, lw1, _p(cw0), _p(cw1), _p(d0), _p(d1),
+             work=_ops._TIMING is not None and (f'ohem2_up_w_bwd P{N * H * W}', _nb(src0, src1, d0, d1) + 9 * N * H * W,
+                                                62 * N * H * W, 'ohem2_bwd_up2_kernel'))
+        return d0, d1
     _run(lib, 'ledn_ohem2_up_bwd', src0, _p(src0), _p(src1), N, Hs, Ws, H, W, ignore_label, _p(work), _p(out), _p(g0), _p(g1),
          lw0, lw1, _p(d0), _p(d1),
          work=_ops._TIMING is not None and (f'ohem2_up_bwd P{N * H * W}', _nb(src0, src1, d0, d1) + 9 * N * H * W,

@@ -871,10 +871,10 @@ def grad_ready(x, tag):
 
 class OhemFn(Function):
     @staticmethod
-    def forward(ctx, logits, target, thres, min_kept, loss_weight, ignore_label):
-        out, work = T.ohem_ce_fwd(logits, target, thres, min_kept, loss_weight, ignore_label)
+    def forward(ctx, logits, target, thres, min_kept, loss_weight, ignore_label, class_weight=None):
+        out, work = T.ohem_ce_fwd(logits, target, thres, min_kept, loss_weight, ignore_label, class_weight=class_weight)
         ctx.save_for_backward(logits, target, work, out)
-        ctx.cfg = (loss_weight, ignore_label)
+        ctx.cfg = (loss_weight, ignore_label, class_weight)
         ctx.mark_non_differentiable(out)
         ctx.set_materialize_grads(False)        # (no zero tensor for the non-differentiable output)
         loss = out[0].clone()   # 0-dim view copy (4 bytes)
@@ -883,8 +883,8 @@ class OhemFn(Function):
     @staticmethod
     def backward(ctx, dloss, _dout):
         logits, target, work, out = ctx.saved_tensors
-        dl = T.ohem_ce_bwd(logits, target, work, out, dloss, ctx.cfg[0], ctx.cfg[1])
-        return dl, None, None, None, None, None
+        dl = T.ohem_ce_bwd(logits, target, work, out, dloss, ctx.cfg[0], ctx.cfg[1], class_weight=ctx.cfg[2])
+        return dl, None, None, None, None, None, None
 
 
 # --------------------------------------------------------------------------- #
@@ -1320,7 +1320,7 @@ def ohem_loss(crit, score, target):
     from .lednet import to_nhwc
     lg = to_nhwc(score, torch.float32)
     loss, _ = OhemFn.apply(lg, target.contiguous(), crit.thresh, crit.min_kept, crit.loss_weight,
-                           crit.ignore_label)
+                           crit.ignore_label, crit.class_weight_on(lg))
     return loss
 
 
@@ -1328,10 +1328,10 @@ class OhemUpFn(Function):
     """OhemCrossEntropy on resize(src -> label size) with the resize folded into the loss kernels (exact 2x)."""
 
     @staticmethod
-    def forward(ctx, src, target, thres, min_kept, loss_weight, ignore_label):
-        out, work = T.ohem_ce_up_fwd(src, target, thres, min_kept, loss_weight, ignore_label)
+    def forward(ctx, src, target, thres, min_kept, loss_weight, ignore_label, class_weight=None):
+        out, work = T.ohem_ce_up_fwd(src, target, thres, min_kept, loss_weight, ignore_label, class_weight=class_weight)
         ctx.save_for_backward(src, target, work, out)
-        ctx.cfg = (loss_weight, ignore_label)
+        ctx.cfg = (loss_weight, ignore_label, class_weight)
         ctx.mark_non_differentiable(out)
         ctx.set_materialize_grads(False)
         loss = out[0].clone()
@@ -1340,7 +1340,8 @@ class OhemUpFn(Function):
     @staticmethod
     def backward(ctx, dloss, _dout):
         src, target, work, out = ctx.saved_tensors
-        return T.ohem_ce_up_bwd(src, target, work, out, dloss, ctx.cfg[0], ctx.cfg[1]), None, None, None, None, None
+        return (T.ohem_ce_up_bwd(src, target, work, out, dloss, ctx.cfg[0], ctx.cfg[1], class_weight=ctx.cfg[2]),
+                None, None, None, None, None, None)
 
 
 class OhemUp2Fn(Function):
@@ -1348,10 +1349,10 @@ class OhemUp2Fn(Function):
     (ledn_ohem2_up_fwd / _bwd): shared label reads (uint8 copy), no per-pixel loss array."""
 
     @staticmethod
-    def forward(ctx, src0, src1, target, cfg0, cfg1, ignore_label):
-        out, work = T.ohem2_up_fwd(src0, src1, target, cfg0, cfg1, ignore_label)
+    def forward(ctx, src0, src1, target, cfg0, cfg1, ignore_label, class_weights=(None, None)):
+        out, work = T.ohem2_up_fwd(src0, src1, target, cfg0, cfg1, ignore_label, class_weights=class_weights)
         ctx.save_for_backward(src0, src1, work, out)
-        ctx.cfg = (cfg0[2], cfg1[2], ignore_label, (int(target.shape[1]), int(target.shape[2])))
+        ctx.cfg = (cfg0[2], cfg1[2], ignore_label, (int(target.shape[1]), int(target.shape[2])), tuple(class_weights))
         ctx.mark_non_differentiable(out)
         ctx.set_materialize_grads(False)
         return out[0, 0].clone(), out[1, 0].clone(), out
@@ -1359,13 +1360,13 @@ class OhemUp2Fn(Function):
     @staticmethod
     def backward(ctx, dl0, dl1, _dout):
         src0, src1, work, out = ctx.saved_tensors
-        lw0, lw1, ign, hw = ctx.cfg
+        lw0, lw1, ign, hw, cws = ctx.cfg
         zero = None
         if dl0 is None or dl1 is None:          # (one of the losses not part of the objective: its gradient is zero)
             zero = torch.zeros(1, dtype=torch.float32, device=src0.device)
         d0, d1 = T.ohem2_up_bwd(src0, src1, hw, work, out, dl0 if dl0 is not None else zero,
-                                dl1 if dl1 is not None else zero, lw0, lw1, ign)
-        return d0, d1, None, None, None, None
+                                dl1 if dl1 is not None else zero, lw0, lw1, ign, class_weights=cws)
+        return d0, d1, None, None, None, None, None
 
 
 FUSE_LOSS_RESIZE = _knob_int('LEDN_FUSE_LOSS_RESIZE', 1)
@@ -1386,6 +1387,7 @@ def led_head_loss_by_feat(h, seg_logits, batch_data_samples):
     hw = label.shape[2:]
     y = label.squeeze(1).contiguous()
     c0, c1 = h.loss_decode[0], h.loss_decode[1]
+    w0, w1 = c0.class_weight_on(xc), c1.class_weight_on(xc)      # None (the default) or the [C] device vector
     H, W = hw
     if FUSE_LOSS_RESIZE and H % 2 == 0 and W % 2 == 0 and xc.shape[-1] == 2:
         # the last (exact 2x) resize of each fused output runs inside the loss kernels: the full-resolution logits
@@ -1393,15 +1395,15 @@ def led_head_loss_by_feat(h, seg_logits, batch_data_samples):
         ctx2, spa2 = fuse_loss_half(xc, h1, h2, hw), fuse_loss_half(xs, h1, h2, hw)
         if (FUSE_LOSS_PAIR and W % 4 == 0 and c0.ignore_label == c1.ignore_label and 0 <= c0.ignore_label <= 255):
             l0, l1, out = OhemUp2Fn.apply(ctx2, spa2, y, (c0.thresh, c0.min_kept, c0.loss_weight),
-                                          (c1.thresh, c1.min_kept, c1.loss_weight), c0.ignore_label)
+                                          (c1.thresh, c1.min_kept, c1.loss_weight), c0.ignore_label, (w0, w1))
             return {'loss_context': l0, 'loss_spatial': l1, 'acc_seg': out[0, 1:2]}
-        l0, out0 = OhemUpFn.apply(ctx2, y, c0.thresh, c0.min_kept, c0.loss_weight, c0.ignore_label)
-        l1, _ = OhemUpFn.apply(spa2, y, c1.thresh, c1.min_kept, c1.loss_weight, c1.ignore_label)
+        l0, out0 = OhemUpFn.apply(ctx2, y, c0.thresh, c0.min_kept, c0.loss_weight, c0.ignore_label, w0)
+        l1, _ = OhemUpFn.apply(spa2, y, c1.thresh, c1.min_kept, c1.loss_weight, c1.ignore_label, w1)
         return {'loss_context': l0, 'loss_spatial': l1, 'acc_seg': out0[1:2]}
     ctx = fuse_loss(xc, h1, h2, hw)
     spa = fuse_loss(xs, h1, h2, hw)
-    l0, out0 = OhemFn.apply(ctx, y, c0.thresh, c0.min_kept, c0.loss_weight, c0.ignore_label)
-    l1, _ = OhemFn.apply(spa, y, c1.thresh, c1.min_kept, c1.loss_weight, c1.ignore_label)
+    l0, out0 = OhemFn.apply(ctx, y, c0.thresh, c0.min_kept, c0.loss_weight, c0.ignore_label, w0)
+    l1, _ = OhemFn.apply(spa, y, c1.thresh, c1.min_kept, c1.loss_weight, c1.ignore_label, w1)
     return {'loss_context': l0, 'loss_spatial': l1, 'acc_seg': out0[1:2]}
 
 
