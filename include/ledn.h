@@ -892,6 +892,37 @@ int ledn_sgd_step(const ledn_sgd_entry* table_dev, int n_tensors, long long max_
                   const float* lr_dev, float momentum, float weight_decay, float grad_scale,
                   void* stream);   /* lr_dev != NULL: learning rate read from device memory (hipGraph replay) */
 
+/* Gradient clipping folded into the SGD step (mmengine optim_wrapper.clip_grad; torch.nn.utils.clip_grad_norm_ with
+ * error_if_nonfinite=False / clip_grad_value_).  Two calls on one stream, no host synchronisation:
+ *
+ * ledn_grad_norm_partials: one streaming pass over the contiguous f32 range g[0..n) (the flat gradient buffer; any
+ *   4-byte aligned pointer) with n_partials workgroups (1..LEDN_CLIP_MAX_PARTIALS); workgroup b writes ONE float to
+ *   partials[b]: its sum of squares (LEDN_NORM_L2) or its largest |g| (LEDN_NORM_INF; a NaN in the input gives NaN, as
+ *   torch.max).  No atomics and one fixed combining order: the same bits on every run, in either determinism mode.
+ *   partials is the caller's own buffer (the stream workspace is overwritten by the next launch that uses it).
+ *
+ * ledn_sgd_step_clip: ledn_sgd_step with the clip applied to grad_scale*g before weight decay and momentum.
+ *   norm_type = LEDN_NORM_L2 / LEDN_NORM_INF: every workgroup combines partials[0..n_partials) in a fixed order,
+ *       total_norm = grad_scale * sqrt(sum)   (L2)      total_norm = grad_scale * max   (inf)
+ *       coef       = min(1, max_norm / (total_norm + 1e-6))
+ *       g' = (grad_scale*coef)*g + wd*p;  m = momentum*m + g';  p -= lr*m;  g = 0
+ *     and norm_out (two device floats, may be NULL) receives {total_norm, coef}.  coef == 1 gives the bits of
+ *     ledn_sgd_step.  A non-finite norm is not masked: coef is NaN and so are the updated parameters.  clip_value is
+ *     ignored.  (total_norm is the norm of the gradient the update uses: with grad_scale = 1/world_size, DDP's mean.)
+ *   norm_type = LEDN_NORM_NONE: clip by value, g' = clamp(grad_scale*g, -clip_value, clip_value) + wd*p (NaN passes, as
+ *     torch.clamp); partials, n_partials, max_norm and norm_out are ignored, no norm pass is needed.
+ * LEDN_EINVAL: n_partials outside 1..LEDN_CLIP_MAX_PARTIALS, an unknown norm_type, max_norm <= 0 (norm modes),
+ * clip_value <= 0 (value mode), NULL buffers. */
+#define LEDN_NORM_NONE 0
+#define LEDN_NORM_L2 2
+#define LEDN_NORM_INF (-1)
+#define LEDN_CLIP_MAX_PARTIALS 256
+int ledn_grad_norm_partials(const float* g, long long n, int norm_type, float* partials, int n_partials, void* stream);
+int ledn_sgd_step_clip(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,
+                       const float* lr_dev, float momentum, float weight_decay, float grad_scale,
+                       const float* partials, int n_partials, int norm_type, float max_norm, float clip_value,
+                       float* norm_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,8 @@ class TtaDesc(C.Structure):            # mirrors ledn_tta_desc
 
 FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 0, 1, 2
 TTA_SOFTMAX, TTA_RAW = 0, 1
+NORM_NONE, NORM_L2, NORM_INF = 0, 2, -1      # include/ledn.h LEDN_NORM_*
+CLIP_MAX_PARTIALS = 256
 
 
 class MfafDesc(C.Structure):
@@ -205,6 +207,9 @@ _PROTOS = {
     'ledn_ohem2_up_w_bwd': ([fp, fp, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, C.c_float, C.c_float, fp, fp, fp, fp,
                              vp], i32),
     'ledn_sgd_step': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, vp], i32),
+    'ledn_grad_norm_partials': ([fp, i64, i32, fp, i32, vp], i32),
+    'ledn_sgd_step_clip': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, fp, i32, i32, C.c_float, C.c_float,
+                            fp, vp], i32),
     'ledn_abi_version': ([], i32),
     'ledn_set_workspace': ([vp, i64], i32),
     'ledn_bind_workspace': ([vp, vp, i64], i32),

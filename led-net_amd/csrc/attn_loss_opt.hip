@@ -907,4 +907,143 @@ int sgd_step_impl(const ledn_sgd_entry* table_dev, int n_tensors, long long max_
     return check_launch();
 }
 
+// ===========================================================================
+// gradient clipping (mmengine OptimWrapper clip_grad = torch.nn.utils.clip_grad_norm_ / clip_grad_value_), folded into the
+// SGD launch.  Pass 1 (grad_norm_partials_kernel): one float per workgroup over the flat gradient buffer -- the sum of
+// squares (L2) or the largest magnitude (inf).  Pass 2 (sgd_clip_kernel): every workgroup sums the <= 256 partials itself
+// in its prologue (the launch boundary is the grid-wide barrier; no finish launch, no ticket), forms the coefficient and
+// runs the SGD update with grad_scale * coef.  No atomics anywhere and one fixed combining order: the norm is the same
+// bits from run to run and in every workgroup, with or without deterministic mode.
+// ===========================================================================
+// torch.max semantics: a NaN on either side wins (fmaxf would drop it)
+__device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
+template <bool INF> __device__ __forceinline__ float norm_acc(float acc, float v) {
+    if constexpr (INF) return nan_max(acc, fabsf(v));
+    else return acc + v * v;
+}
+template <bool INF> __device__ __forceinline__ float norm_acc4(float acc, const float4& v) {
+    return norm_acc<INF>(norm_acc<INF>(norm_acc<INF>(norm_acc<INF>(acc, v.x), v.y), v.z), v.w);
+}
+// combines one value per thread of a 256-thread workgroup: xor butterfly inside each wave, then the four wave results in
+// wave order through LDS.  Every thread returns the same bits.  (Both operations are commutative, so the butterfly leaves
+// one value in all 64 lanes.)
+template <bool INF> __device__ __forceinline__ float block256_combine(float v, float* s_w) {
+    if constexpr (INF) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) v = nan_max(v, __shfl_xor(v, m));
+    } else {
+        v = wave_sum(v);
+    }
+    if (lane_id() == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = s_w[0];
+    if constexpr (INF) r = nan_max(nan_max(nan_max(r, s_w[1]), s_w[2]), s_w[3]);
+    else r = ((r + s_w[1]) + s_w[2]) + s_w[3];
+    return r;
+}
+
+// grid-stride over the 16-byte vectors of g[head .. head + 4 nvec) (head = the 0-3 floats in front of the first aligned
+// address); the head and the 0-3 tail floats go to the first threads of workgroup 0.  The loop body takes four vectors per
+// trip so that four loads are in flight, and accumulates them in index order: the same sum as one vector per trip.
+template <bool INF>
+__global__ void __launch_bounds__(256) grad_norm_partials_kernel(const float* g, long n, int head, float* partials) {
+    __shared__ float s_w[4];
+    const int t = threadIdx.x;
+    const long nvec = (n - head) >> 2;
+    const int tail = (int)(n - head - (nvec << 2));
+    const float4* gv = reinterpret_cast<const float4*>(g + head);
+    const long stride = (long)gridDim.x * 256;
+    float acc = 0.f;
+    long v = (long)blockIdx.x * 256 + t;
+    for (; v + 3 * stride < nvec; v += 4 * stride) {
+        const float4 a = gv[v], b = gv[v + stride], c = gv[v + 2 * stride], d = gv[v + 3 * stride];
+        acc = norm_acc4<INF>(norm_acc4<INF>(norm_acc4<INF>(norm_acc4<INF>(acc, a), b), c), d);
+    }
+    for (; v < nvec; v += stride) acc = norm_acc4<INF>(acc, gv[v]);
+    if (blockIdx.x == 0) {
+        if (t < head) acc = norm_acc<INF>(acc, g[t]);
+        if (t < tail) acc = norm_acc<INF>(acc, g[head + (nvec << 2) + t]);
+    }
+    acc = block256_combine<INF>(acc, s_w);
+    if (t == 0) partials[blockIdx.x] = acc;
+}
+
+int grad_norm_partials_impl(const float* g, long long n, int norm_type, float* partials, int n_partials, hipStream_t s) {
+    LEDN_REQUIRE(g && partials && n > 0 && ((uintptr_t)g & 3u) == 0);
+    LEDN_REQUIRE(n_partials >= 1 && n_partials <= LEDN_CLIP_MAX_PARTIALS);
+    LEDN_REQUIRE(norm_type == LEDN_NORM_L2 || norm_type == LEDN_NORM_INF);
+    long head = (long)((16u - ((uintptr_t)g & 15u)) & 15u) >> 2;
+    if (head > n) head = n;
+    if (norm_type == LEDN_NORM_INF)
+        LEDN_LAUNCH(grad_norm_partials_kernel<true>, dim3((unsigned)n_partials), dim3(256), 0, s, g, (long)n, (int)head, partials);
+    else
+        LEDN_LAUNCH(grad_norm_partials_kernel<false>, dim3((unsigned)n_partials), dim3(256), 0, s, g, (long)n, (int)head, partials);
+    return check_launch();
+}
+
+// MODE: LEDN_NORM_L2 / LEDN_NORM_INF = clip by the total norm behind `partials`, LEDN_NORM_NONE = clip by value.
+// (sgd_kernel above stays the unclipped instance, untouched.)
+template <int MODE>
+__global__ void __launch_bounds__(256) sgd_clip_kernel(const ledn_sgd_entry* table, float lr_arg, const float* lr_dev,
+                                                       float momentum, float wd, float gscale, const float* partials,
+                                                       int n_partials, float max_norm, float clip_value, float* norm_out) {
+    const ledn_sgd_entry e = table[blockIdx.y];
+    if ((long)blockIdx.x * blockDim.x >= e.n) return;      // (whole workgroup: nothing of this tensor is its to update)
+    const float lr = lr_dev ? *lr_dev : lr_arg;
+    float gs = gscale;
+    if constexpr (MODE != LEDN_NORM_NONE) {
+        __shared__ float s_w[4];
+        const int t = threadIdx.x;
+        float tot = block256_combine<MODE == LEDN_NORM_INF>(t < n_partials ? partials[t] : 0.f, s_w);
+        if constexpr (MODE == LEDN_NORM_L2) tot = sqrtf(tot);
+        tot *= gscale;                                     // the norm of the gradient the update uses (DDP's mean)
+        const float c = max_norm / (tot + 1e-6f);
+        const float coef = c > 1.f ? 1.f : c;              // torch.clamp(max=1): a NaN coefficient stays NaN
+        if (norm_out && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {
+            norm_out[0] = tot;
+            norm_out[1] = coef;
+        }
+        gs = gscale * coef;
+    }
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < e.n; i += stride) {
+        const float p = e.p[i];
+        float g;
+        if constexpr (MODE == LEDN_NORM_NONE) {
+            const float sg = e.g[i] * gs;
+            g = (sg < -clip_value ? -clip_value : (sg > clip_value ? clip_value : sg)) + wd * p;   // torch.clamp: NaN passes
+        } else {
+            g = e.g[i] * gs + wd * p;
+        }
+        const float m = momentum * e.m[i] + g;
+        e.m[i] = m;
+        e.p[i] = p - lr * m;
+        e.g[i] = 0.f;
+    }
+}
+
+int sgd_step_clip_impl(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr, const float* lr_dev,
+                       float momentum, float weight_decay, float grad_scale, const float* partials, int n_partials,
+                       int norm_type, float max_norm, float clip_value, float* norm_out, hipStream_t s) {
+    LEDN_REQUIRE(table_dev && n_tensors > 0 && max_n > 0);
+    LEDN_REQUIRE(norm_type == LEDN_NORM_L2 || norm_type == LEDN_NORM_INF || norm_type == LEDN_NORM_NONE);
+    if (norm_type == LEDN_NORM_NONE) {
+        LEDN_REQUIRE(clip_value > 0.f);
+    } else {
+        LEDN_REQUIRE(partials && n_partials >= 1 && n_partials <= LEDN_CLIP_MAX_PARTIALS && max_norm > 0.f);
+    }
+    long chunks = cdiv(max_n, 256 * 8);
+    if (chunks > 64) chunks = 64;
+    const dim3 grid((unsigned)chunks, (unsigned)n_tensors);
+#define LEDN_SGD_CLIP(MODE)                                                                                          \
+    LEDN_LAUNCH(sgd_clip_kernel<MODE>, grid, dim3(256), 0, s, table_dev, lr, lr_dev, momentum, weight_decay, grad_scale, \
+                partials, n_partials, max_norm, clip_value, norm_out)
+    if (norm_type == LEDN_NORM_L2) LEDN_SGD_CLIP(LEDN_NORM_L2);
+    else if (norm_type == LEDN_NORM_INF) LEDN_SGD_CLIP(LEDN_NORM_INF);
+    else LEDN_SGD_CLIP(LEDN_NORM_NONE);
+#undef LEDN_SGD_CLIP
+    return check_launch();
+}
+
 }  // namespace ledn

@@ -134,6 +134,10 @@ int slide_finish_impl(float* canvas, const int* rowcnt, const int* colcnt, unsig
                       int W, hipStream_t s);
 int sgd_step_impl(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,
                   const float* lr_dev, float momentum, float weight_decay, float grad_scale, hipStream_t s);
+int grad_norm_partials_impl(const float* g, long long n, int norm_type, float* partials, int n_partials, hipStream_t s);
+int sgd_step_clip_impl(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr, const float* lr_dev,
+                       float momentum, float weight_decay, float grad_scale, const float* partials, int n_partials,
+                       int norm_type, float max_norm, float clip_value, float* norm_out, hipStream_t s);
 }  // namespace ledn
 
 #include <mutex>
@@ -584,6 +588,16 @@ int ledn_sgd_step(const ledn_sgd_entry* table_dev, int n_tensors, long long max_
                   const float* lr_dev, float momentum, float weight_decay, float grad_scale, void* stream) {
     return sgd_step_impl(table_dev, n_tensors, max_n, lr, lr_dev, momentum, weight_decay, grad_scale,
                          S(stream));
+}
+int ledn_grad_norm_partials(const float* g, long long n, int norm_type, float* partials, int n_partials, void* stream) {
+    return grad_norm_partials_impl(g, n, norm_type, partials, n_partials, S(stream));
+}
+int ledn_sgd_step_clip(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,
+                       const float* lr_dev, float momentum, float weight_decay, float grad_scale,
+                       const float* partials, int n_partials, int norm_type, float max_norm, float clip_value,
+                       float* norm_out, void* stream) {
+    return sgd_step_clip_impl(table_dev, n_tensors, max_n, lr, lr_dev, momentum, weight_decay, grad_scale, partials,
+                              n_partials, norm_type, max_norm, clip_value, norm_out, S(stream));
 }
 
 }  // extern "C"

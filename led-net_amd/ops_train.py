@@ -763,10 +763,58 @@ class SgdTable:
         self.ref = params[0]
         self.keep = (params, grads, moms)
 
-    def step(self, lr, momentum, weight_decay, grad_scale=1.0, lr_dev=None):
+    def step(self, lr, momentum, weight_decay, grad_scale=1.0, lr_dev=None, clip=None):
+        """clip: None (the plain ledn_sgd_step launch) or a GradClip whose norm pass (grad_norm_partials into
+        clip.partials) has been queued on this stream, or one that clips by value"""
         lib = _lib.get_lib()
-        _run(lib, 'ledn_sgd_step', self.ref, self.table.data_ptr(), self.n, self.max_n, float(lr), _p(lr_dev),
-             momentum, weight_decay, grad_scale, work=_ops._TIMING is not None and (f'sgd {self.n} tensors', 16 * sum(p.numel() for p in self.keep[0]), 0))
+        work = _ops._TIMING is not None and (f'sgd {self.n} tensors', 16 * sum(p.numel() for p in self.keep[0]), 0)
+        if clip is None:
+            _run(lib, 'ledn_sgd_step', self.ref, self.table.data_ptr(), self.n, self.max_n, float(lr), _p(lr_dev),
+                 momentum, weight_decay, grad_scale, work=work)
+            return
+        _check(lib, clip.buf)
+        by_norm = clip.norm_type != _lib.NORM_NONE
+        _run(lib, 'ledn_sgd_step_clip', self.ref, self.table.data_ptr(), self.n, self.max_n, float(lr), _p(lr_dev),
+             momentum, weight_decay, grad_scale, _p(clip.partials) if by_norm else None, clip.n_partials, clip.norm_type,
+             float(clip.max_norm), float(clip.clip_value), _p(clip.norm_out) if by_norm else None,
+             work=work and (work[0] + ' clip', work[1], 0, 'sgd_clip_kernel'))
+
+
+def norm_partials_count(n):
+    """workgroups of the norm pass over n floats: 4096 floats (four 16-byte loads per thread) each, at most 256"""
+    return max(1, min(_lib.CLIP_MAX_PARTIALS, -(-int(n) // 4096)))
+
+
+def grad_norm_partials(flat, norm_type, partials):
+    """One streaming pass over the contiguous f32 tensor `flat`: partials[b] = workgroup b's sum of squares
+    (NORM_L2) or largest magnitude (NORM_INF), b < partials.numel() <= 256.  The total -- the sum / the maximum of
+    the partials -- is formed by ledn_sgd_step_clip in its prologue (SgdTable.step(clip=...))."""
+    lib = _lib.get_lib()
+    if flat.dtype != torch.float32 or partials.dtype != torch.float32:
+        raise LednError('grad_norm_partials: float32 tensors only')
+    _check(lib, flat, partials)
+    _run(lib, 'ledn_grad_norm_partials', flat, flat.data_ptr(), flat.numel(), int(norm_type), partials.data_ptr(),
+         partials.numel(), work=_ops._TIMING is not None and (f'grad norm {flat.numel()}', 4 * flat.numel(), 0,
+                                                                'grad_norm_partials_kernel'))
+    return partials
+
+
+class GradClip:
+    """Device state of gradient clipping for SgdTable.step: ONE persistent f32 buffer [partials | total_norm | coef]
+    (its own allocation: the stream workspace is overwritten by whatever launches next).
+    norm_type NORM_L2 / NORM_INF with max_norm, or NORM_NONE with clip_value (clip by value: no norm pass)."""
+
+    def __init__(self, device, n, norm_type=_lib.NORM_L2, max_norm=0.0, clip_value=0.0):
+        self.norm_type, self.max_norm, self.clip_value = int(norm_type), float(max_norm), float(clip_value)
+        self.n_partials = norm_partials_count(n) if self.norm_type != _lib.NORM_NONE else 0
+        self.buf = torch.zeros(self.n_partials + 2, dtype=torch.float32, device=device)
+        self.partials = self.buf[:self.n_partials]
+        self.norm_out = self.buf[self.n_partials:]
+        self.total_norm, self.coef = self.norm_out[0], self.norm_out[1]       # 0-dim views: current after every step
+
+    def norm_pass(self, flat):
+        if self.norm_type != _lib.NORM_NONE:
+            grad_norm_partials(flat, self.norm_type, self.partials)
 
 
 class PackTable:

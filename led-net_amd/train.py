@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import ops, ops_train as T
+from . import _lib, ops, ops_train as T
 from .ops import ACT_NONE, ACT_PRELU, ACT_RELU, ACT_RELU6, RES_ADD, RES_GATE, RES_NONE
 
 from ._env import knob_int as _knob_int  # noqa: E402
@@ -1417,6 +1417,49 @@ def led_head_loss(h, inputs, batch_data_samples):
 # --------------------------------------------------------------------------- #
 # Trainer: SGD(momentum, wd) + PolyLR + data-parallel gradient all-reduce
 # --------------------------------------------------------------------------- #
+def parse_clip_grad(clip_grad):
+    """mmengine OptimWrapper's ``clip_grad`` -> None or ('norm', norm_type, max_norm) / ('value', clip_value):
+    dict(max_norm=, norm_type=2) and dict(type='norm', ...) are torch.nn.utils.clip_grad_norm_'s arguments,
+    dict(type='value', clip_value=) clip_grad_value_'s.  norm_type: 2, 2.0, 'inf' or float('inf')."""
+    if clip_grad is None:
+        return None
+    if not isinstance(clip_grad, dict):
+        raise ValueError(f'clip_grad must be None or a dict, got {type(clip_grad).__name__}')
+    cg = dict(clip_grad)
+    kind = cg.pop('type', 'norm')
+    if kind not in ('norm', 'value'):
+        raise ValueError(f"clip_grad: type={kind!r} (expected 'norm' or 'value')")
+    if kind == 'value':
+        unknown = sorted(set(cg) - {'clip_value', 'foreach'})
+        if unknown:
+            raise ValueError(f"clip_grad (type='value'): unknown key {unknown[0]!r}")
+        if 'clip_value' not in cg:
+            raise ValueError("clip_grad (type='value'): clip_value is required")
+        v = float(cg['clip_value'])
+        if not v > 0:
+            raise ValueError(f'clip_grad: clip_value={cg["clip_value"]!r} must be > 0')
+        return ('value', v)
+    unknown = sorted(set(cg) - {'max_norm', 'norm_type', 'error_if_nonfinite', 'foreach'})
+    if unknown:
+        raise ValueError(f'clip_grad: unknown key {unknown[0]!r}')
+    if cg.get('error_if_nonfinite', False):
+        raise ValueError('clip_grad: error_if_nonfinite=True is not supported (it needs a device-to-host read of the norm '
+                         'in every step; the step is one captured graph without host synchronisation)')
+    if 'max_norm' not in cg:
+        raise ValueError('clip_grad: max_norm is required')
+    m = float(cg['max_norm'])
+    if not m > 0:
+        raise ValueError(f'clip_grad: max_norm={cg["max_norm"]!r} must be > 0')
+    nt = cg.get('norm_type', 2)
+    if isinstance(nt, str):
+        if nt != 'inf':
+            raise ValueError(f"clip_grad: norm_type={nt!r} (supported: 2 and 'inf')")
+        nt = math.inf
+    if isinstance(nt, bool) or not isinstance(nt, (int, float)) or nt not in (2, math.inf):
+        raise ValueError(f"clip_grad: norm_type={nt!r} (supported: 2 and 'inf')")
+    return ('norm', _lib.NORM_INF if nt == math.inf else _lib.NORM_L2, m)
+
+
 class Trainer:
     """One process per GPU.  Gradients live in ONE flat f32 buffer (parameter
     ``.grad`` tensors are views of it): a single multi-tensor SGD launch updates
@@ -1424,8 +1467,12 @@ class Trainer:
     large RCCL all-reduces over contiguous slices instead of one per tensor."""
 
     def __init__(self, model, cfg=None, world_size=1, lr=None, momentum=None, weight_decay=None,
-                 max_iters=None, power=0.9, eta_min=0.0, bucket_mb=2.0, direct_grads=True, collectives=None):
+                 max_iters=None, power=0.9, eta_min=0.0, bucket_mb=2.0, direct_grads=True, collectives=None,
+                 clip_grad=None):
         opt = dict((cfg or {}).get('optimizer', {}))
+        if clip_grad is None:       # config: optim_wrapper = dict(type='OptimWrapper', optimizer=..., clip_grad=...)
+            clip_grad = ((cfg or {}).get('optim_wrapper') or {}).get('clip_grad')
+        clip = parse_clip_grad(clip_grad)
         self.model = model
         self.base_lr = lr if lr is not None else opt.get('lr', 0.01)
         self.momentum = momentum if momentum is not None else opt.get('momentum', 0.9)
@@ -1454,6 +1501,9 @@ class Trainer:
             self.moms.append(self.flat_mom[off:off + k].view_as(p))
             off += k
         self.table = None
+        # gradient clipping: the norm pass over flat_grad writes its per-workgroup partials into the trainer's own
+        # persistent buffer [partials | total_norm | coef]; the SGD launch combines them in its prologue
+        self._set_clip(clip)
         self.direct_grads = direct_grads     # backward kernels reduce into the flat gradient buffer
         self._sink_map = {}
         self._arena = ops.ZeroArena(dev)
@@ -1511,6 +1561,20 @@ class Trainer:
         self._ready = {}
         self._early_done = False
         self.overlap_exchange = bool(_knob_int('LEDN_OVERLAP_EXCHANGE', 1)) and not self._single_stream
+
+    def _set_clip(self, clip):
+        dev, n = self.flat_grad.device, self.flat_grad.numel()
+        self.clip = None
+        if clip is not None and clip[0] == 'norm':
+            self.clip = T.GradClip(dev, n, norm_type=clip[1], max_norm=clip[2])
+        elif clip is not None:
+            self.clip = T.GradClip(dev, n, norm_type=_lib.NORM_NONE, clip_value=clip[1])
+
+    def set_clip_grad(self, clip_grad):
+        """change (or switch off, None) gradient clipping between eager steps; a captured graph holds the launches
+        of the setting it was captured with, so capture() again afterwards"""
+        assert self._graph is None, 'set_clip_grad after capture(): the graph replays the old setting'
+        self._set_clip(parse_clip_grad(clip_grad))
 
     @property
     def _all_reduce(self):      # (bench.py / older callers: "does this trainer exchange gradients")
@@ -1719,12 +1783,21 @@ class Trainer:
                 torch.cuda.current_stream(self.flat_grad.device).wait_stream(self._gstream)
         if self._lr_dev is not None and not torch.cuda.is_current_stream_capturing():
             self._lr_dev.fill_(self.lr())       # eager step after a capture(): keep the device-resident rate current
-        self.table.step(self.lr(), self.momentum, self.wd, 1.0 / self.world, lr_dev=self._lr_dev)
+        if self.clip is None:
+            self.table.step(self.lr(), self.momentum, self.wd, 1.0 / self.world, lr_dev=self._lr_dev)
+        else:
+            # after the exchange (and the wait for its stream): the norm of the all-reduced gradient, the same on every rank
+            self.clip.norm_pass(self.flat_grad)
+            self.table.step(self.lr(), self.momentum, self.wd, 1.0 / self.world, lr_dev=self._lr_dev, clip=self.clip)
         self.iter += 1
         # detached: a caller holding the returned losses would otherwise keep the step's autograd graph
         # (and its AccumulateGrad nodes, bound to this step's stream) alive into a later hipGraph capture,
         # where they run on the wrong stream and break the capture
-        return {k: v.detach() for k, v in losses.items()}
+        out = {k: v.detach() for k, v in losses.items()}
+        if self.clip is not None and self.clip.norm_type != _lib.NORM_NONE:
+            out['grad_norm'] = self.clip.total_norm     # (mmengine's log key; a view of the persistent buffer: a captured
+            # graph's _static_out shows the value of each replay)
+        return out
 
     # ------------------------------------------------------------------ #
     # hipGraph replay of the whole step (forward + loss + backward + SGD): ~800 launches

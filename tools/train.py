@@ -62,7 +62,12 @@ def main():
         node = cfg
         parts = key.split('.')
         for part in parts[:-1]:
-            node = node[int(part)] if isinstance(node, list) else node[part]
+            if isinstance(node, list):
+                node = node[int(part)]
+                continue
+            if node.get(part) is None:      # optim_wrapper.clip_grad.max_norm=1.0 on a config without that section (or
+                node[part] = {}             # with clip_grad=None): the override creates the node, as mmengine's merge does
+            node = node[part]
         try:
             val = ast.literal_eval(val)   # numbers / tuples / lists / None / booleans, as mmengine's DictAction
         except (ValueError, SyntaxError):  # plain string
