@@ -923,6 +923,63 @@ int ledn_sgd_step_clip(const ledn_sgd_entry* table_dev, int n_tensors, long long
                        const float* partials, int n_partials, int norm_type, float max_norm, float clip_value,
                        float* norm_out, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Generalised multi-tensor optimizer step: SGD or AdamW with a learning-rate and a weight-decay multiplier per tensor
+ * (mmengine optim_wrapper.paramwise_cfg), a two-scalar schedule and the clipping of ledn_sgd_step_clip, in ONE launch.
+ * (ledn_sgd_step / ledn_sgd_step_clip above stay what a plain SGD configuration runs.)
+ *
+ * Per tensor i:   lr_i = lr_mult_i * A + B        wd_i = wd_mult_i * weight_decay
+ *   A, B: lr_a / lr_b, or sched_dev[0..1] when sched_dev != NULL.  Every supported scheduler list (LinearLR, PolyLR,
+ *   ConstantLR by iteration) gives a group of base rate lr_mult_i * base_lr the rate lr_mult_i * A(t) + B(t).
+ *   s = grad_scale * coef (clip by norm, coef as in ledn_sgd_step_clip from `partials`, {total_norm, coef} to norm_out),
+ *   g' = s*g, or clamp(grad_scale*g, -clip_value, clip_value) (clip by value), or grad_scale*g (LEDN_CLIP_OFF).
+ * LEDN_OPTIM_SGD   (torch.optim.SGD):   g'' = g' + wd_i*p;  m = momentum*m + g'';  p -= lr_i*m;  g = 0
+ *   With every multiplier 1 and B = 0: the bits of ledn_sgd_step (ledn_sgd_step_clip when clipping).
+ * LEDN_OPTIM_ADAMW (torch.optim.AdamW, amsgrad=False, maximize=False):
+ *   p *= 1 - lr_i*wd_i;  m = beta1*m + (1-beta1)*g';  v = beta2*v + (1-beta2)*g'^2;
+ *   p -= (lr_i/bc1) * m / (sqrt(v)/sqrt_bc2 + eps);  g = 0
+ *   bc1 = 1 - beta1^t, sqrt_bc2 = sqrt(1 - beta2^t), t the 1-based step count: bc1 / sqrt_bc2 of the descriptor, or
+ *   sched_dev[2..3] when sched_dev != NULL (sched_dev: four device floats {A, B, bc1, sqrt_bc2}; a captured graph
+ *   replays the whole schedule by refreshing them).
+ * No atomics: the same bits on every run in either determinism mode.  16-byte accesses for every tensor whose p, g, m
+ * (and v) are all 16-byte aligned, 4-byte accesses otherwise -- the result does not depend on which.
+ * LEDN_EINVAL: unknown kind or clip, beta1 / beta2 outside [0, 1), eps <= 0, AdamW without second moments (has_v == 0:
+ * the table is device memory, the caller states whether its v pointers are filled in), AdamW with neither sched_dev nor
+ * positive bc1 / sqrt_bc2, and the clip checks of ledn_sgd_step_clip. */
+#define LEDN_OPTIM_SGD 0
+#define LEDN_OPTIM_ADAMW 1
+#define LEDN_CLIP_OFF 0
+#define LEDN_CLIP_NORM 1      /* by total norm: norm_type LEDN_NORM_L2 / LEDN_NORM_INF */
+#define LEDN_CLIP_VALUE 2
+typedef struct {
+    float* p;
+    float* g;
+    float* m;           /* SGD: momentum buffer; AdamW: exp_avg */
+    float* v;           /* AdamW: exp_avg_sq; NULL for SGD */
+    long long n;
+    float lr_mult;
+    float wd_mult;
+} ledn_optim_entry;
+typedef struct {
+    int kind;           /* LEDN_OPTIM_* */
+    int has_v;
+    float lr_a, lr_b;
+    const float* sched_dev;
+    float momentum;     /* SGD */
+    float eps;          /* AdamW ... */
+    double beta1, beta2;
+    float bc1, sqrt_bc2;
+    float weight_decay, grad_scale;
+    int clip;           /* LEDN_CLIP_* */
+    int norm_type;
+    const float* partials;
+    int n_partials;
+    float max_norm, clip_value;
+    float* norm_out;
+} ledn_optim_desc;
+int ledn_optim_step(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

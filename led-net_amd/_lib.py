@@ -119,6 +119,8 @@ FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 0, 1, 2
 TTA_SOFTMAX, TTA_RAW = 0, 1
 NORM_NONE, NORM_L2, NORM_INF = 0, 2, -1      # include/ledn.h LEDN_NORM_*
 CLIP_MAX_PARTIALS = 256
+OPTIM_SGD, OPTIM_ADAMW = 0, 1                # LEDN_OPTIM_*
+CLIP_OFF, CLIP_NORM, CLIP_VALUE = 0, 1, 2    # LEDN_CLIP_*
 
 
 class MfafDesc(C.Structure):
@@ -170,6 +172,18 @@ class SgdEntry(C.Structure):
     _fields_ = [('p', fp), ('g', fp), ('m', fp), ('n', i64)]
 
 
+class OptimEntry(C.Structure):          # mirrors ledn_optim_entry
+    _fields_ = [('p', fp), ('g', fp), ('m', fp), ('v', fp), ('n', i64), ('lr_mult', C.c_float), ('wd_mult', C.c_float)]
+
+
+class OptimDesc(C.Structure):           # mirrors ledn_optim_desc
+    _fields_ = [('kind', i32), ('has_v', i32), ('lr_a', C.c_float), ('lr_b', C.c_float), ('sched_dev', fp),
+                ('momentum', C.c_float), ('eps', C.c_float), ('beta1', C.c_double), ('beta2', C.c_double),
+                ('bc1', C.c_float), ('sqrt_bc2', C.c_float), ('weight_decay', C.c_float), ('grad_scale', C.c_float),
+                ('clip', i32), ('norm_type', i32), ('partials', fp), ('n_partials', i32), ('max_norm', C.c_float),
+                ('clip_value', C.c_float), ('norm_out', fp)]
+
+
 _PROTOS = {
     'ledn_bn_act_bwd_reduce': ([C.POINTER(BnBwdDesc), vp], i32),
     'ledn_bn_act_bwd_apply': ([C.POINTER(BnBwdDesc), vp], i32),
@@ -210,6 +224,7 @@ _PROTOS = {
     'ledn_grad_norm_partials': ([fp, i64, i32, fp, i32, vp], i32),
     'ledn_sgd_step_clip': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, fp, i32, i32, C.c_float, C.c_float,
                             fp, vp], i32),
+    'ledn_optim_step': ([vp, i32, i64, C.POINTER(OptimDesc), vp], i32),
     'ledn_abi_version': ([], i32),
     'ledn_set_workspace': ([vp, i64], i32),
     'ledn_bind_workspace': ([vp, vp, i64], i32),

@@ -39,8 +39,9 @@ def load_checkpoint(model, filename, map_location='cpu', strict=False):
 
 def save_checkpoint(model, filename, meta=None, trainer=None):
     """mmengine layout: {'meta': ..., 'state_dict': cpu tensors} and, with a Trainer, the keys mmengine's
-    CheckpointHook adds and Runner.resume reads: 'optimizer' (torch.optim.SGD.state_dict(): the momentum buffers,
-    indexed by position in model.parameters()), 'param_schedulers' (the PolyLR position), 'message_hub'
+    CheckpointHook adds and Runner.resume reads: 'optimizer' (torch.optim.SGD.state_dict() / AdamW.state_dict(): the
+    momentum buffers or both moments and the step, indexed by position in model.parameters(); one param group, or one
+    per parameter under a paramwise_cfg), 'param_schedulers' (one dict per scheduler of the config's list), 'message_hub'
     (runtime_info iter / epoch / max_iters) and meta['epoch' | 'iter' | 'seed' | 'experiment_name'].  The layout is
     restated from mmengine's documented checkpoint format (mmengine is not installed here: no file written by
     the reference stack pins it)."""
@@ -49,7 +50,7 @@ def save_checkpoint(model, filename, meta=None, trainer=None):
     ckpt['meta'].setdefault('epoch', 0)
     if trainer is not None:
         ckpt['optimizer'] = trainer.optimizer_state_dict()
-        ckpt['param_schedulers'] = [trainer.scheduler_state_dict()]
+        ckpt['param_schedulers'] = trainer.scheduler_state_dicts()
         ckpt['meta'].setdefault('iter', trainer.iter)
         ckpt['meta'].setdefault('seed', 304)
         ckpt['meta'].setdefault('experiment_name', 'led_net_amd')

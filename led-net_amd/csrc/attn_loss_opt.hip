@@ -1046,4 +1046,208 @@ int sgd_step_clip_impl(const ledn_sgd_entry* table_dev, int n_tensors, long long
     return check_launch();
 }
 
+// ===========================================================================
+// generalised multi-tensor optimizer step (ledn_optim_step): SGD or AdamW, a learning-rate and a weight-decay multiplier
+// per tensor (mmengine paramwise_cfg), the rate as lr_mult * A + B (A, B: the two scalars every supported schedule
+// collapses to), clipping folded in as in sgd_clip_kernel.  grid = (chunks, tensors) as sgd_kernel.  A tensor whose
+// p / g / m / v pointers are all 16-byte aligned moves as float4 (the 0-3 tail floats go to the first threads of chunk 0);
+// any other tensor takes the scalar loop.  Both paths run the same per-element expressions, so the path taken never
+// changes a bit.  No atomics, no cross-workgroup reduction: the same bits on every run in both determinism modes.
+// (sgd_kernel / sgd_clip_kernel above stay what a plain SGD configuration launches, untouched.)
+// ===========================================================================
+enum { OPT_CLIP_OFF = 0, OPT_CLIP_L2 = 1, OPT_CLIP_INF = 2, OPT_CLIP_VALUE = 3 };
+
+struct OptimArgs {
+    const ledn_optim_entry* table;
+    const float* sched_dev;            // NULL or {A, B, bc1, sqrt(bc2)} on the device (a captured graph replays the schedule)
+    float A, B, bc1, sbc2;
+    float momentum, b1, omb1, b2, omb2, eps;
+    float weight_decay, gscale;
+    const float* partials;
+    int n_partials;
+    float max_norm, clip_value;
+    float* norm_out;
+};
+
+struct OptimConsts {                   // per tensor, per thread: formed once in front of the loop
+    float gs, cv, lr, wd, mom, decay, b1, omb1, b2, omb2, step, sbc2, eps;
+};
+
+// The roundings are written out, not left to -ffp-contract: which product the compiler fuses into which sum depends on the
+// loop around the expression (sgd_kernel's a * b + c * d + e * f comes out as rn(mom * m) + fma(gs, g, rn(wd * p)), the same
+// text inside another loop does not), and the SGD form has to give the bits of sgd_kernel / sgd_clip_kernel from the float4
+// loop and the scalar loop alike.  The emulator's host compiler fuses nothing, there and here.
+#ifdef LEDN_CPU_EMU
+__device__ __forceinline__ float opt_fma(float a, float b, float c) { return a * b + c; }
+#else
+__device__ __forceinline__ float opt_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+#endif
+__device__ __forceinline__ float opt_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float opt_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+template <int KIND, int CLIP>
+__device__ __forceinline__ void optim_update(const OptimConsts& c, float& p, float g, float& m, float& v) {
+    if constexpr (KIND == LEDN_OPTIM_SGD) {
+        const float wp = opt_mul(c.wd, p);
+        float gg;
+        if constexpr (CLIP == OPT_CLIP_VALUE) {
+            const float sg = opt_mul(g, c.gs);
+            gg = opt_add(wp, sg < -c.cv ? -c.cv : (sg > c.cv ? c.cv : sg));       // torch.clamp: NaN passes
+        } else {
+            gg = opt_fma(g, c.gs, wp);
+        }
+        m = opt_add(opt_mul(c.mom, m), gg);
+        p = opt_fma(-c.lr, m, p);
+    } else {
+        float sg = opt_mul(g, c.gs);
+        if constexpr (CLIP == OPT_CLIP_VALUE) sg = sg < -c.cv ? -c.cv : (sg > c.cv ? c.cv : sg);
+        p = opt_mul(p, c.decay);
+        m = opt_fma(c.b1, m, opt_mul(c.omb1, sg));
+        v = opt_fma(c.b2, v, opt_mul(c.omb2, opt_mul(sg, sg)));
+        p = opt_add(p, -(opt_mul(c.step, m) / opt_add(sqrtf(v) / c.sbc2, c.eps)));
+    }
+}
+
+template <int KIND, int CLIP>
+__global__ void __launch_bounds__(256) optim_kernel(const OptimArgs a) {
+    const ledn_optim_entry e = a.table[blockIdx.y];
+    const bool vec = ((((uintptr_t)e.p | (uintptr_t)e.g | (uintptr_t)e.m | (uintptr_t)e.v) & 15u) == 0) && e.n >= 4;
+    // (whole workgroup: nothing of this tensor is its to update; chunk 0 always stays, it owns the tail)
+    if ((long)blockIdx.x * blockDim.x * (vec ? 4 : 1) >= e.n) return;
+    const int t = threadIdx.x;
+    float A = a.A, B = a.B, bc1 = a.bc1, sbc2 = a.sbc2;
+    if (a.sched_dev) {
+        A = a.sched_dev[0];
+        B = a.sched_dev[1];
+        if constexpr (KIND == LEDN_OPTIM_ADAMW) {
+            bc1 = a.sched_dev[2];
+            sbc2 = a.sched_dev[3];
+        }
+    }
+    OptimConsts c;
+    c.gs = a.gscale;
+    if constexpr (CLIP == OPT_CLIP_L2 || CLIP == OPT_CLIP_INF) {
+        __shared__ float s_w[4];
+        float tot = block256_combine<CLIP == OPT_CLIP_INF>(t < a.n_partials ? a.partials[t] : 0.f, s_w);
+        if constexpr (CLIP == OPT_CLIP_L2) tot = sqrtf(tot);
+        tot *= a.gscale;                                   // the norm of the gradient the update uses (DDP's mean)
+        const float q = a.max_norm / (tot + 1e-6f);
+        const float coef = q > 1.f ? 1.f : q;              // torch.clamp(max=1): a NaN coefficient stays NaN
+        if (a.norm_out && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {
+            a.norm_out[0] = tot;
+            a.norm_out[1] = coef;
+        }
+        c.gs = a.gscale * coef;
+    }
+    c.cv = a.clip_value;
+    c.lr = e.lr_mult * A + B;
+    c.wd = e.wd_mult * a.weight_decay;
+    c.mom = a.momentum;
+    c.decay = 1.f - c.lr * c.wd;
+    c.b1 = a.b1, c.omb1 = a.omb1, c.b2 = a.b2, c.omb2 = a.omb2;
+    c.step = c.lr / bc1;
+    c.sbc2 = sbc2;
+    c.eps = a.eps;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long i0 = (long)blockIdx.x * blockDim.x + t;
+    if (vec) {
+        const long nvec = e.n >> 2;
+        float4* pv = reinterpret_cast<float4*>(e.p);
+        float4* gv = reinterpret_cast<float4*>(e.g);
+        float4* mv = reinterpret_cast<float4*>(e.m);
+        float4* vv = reinterpret_cast<float4*>(e.v);
+        for (long i = i0; i < nvec; i += stride) {
+            float4 p = pv[i], m = mv[i], v = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 g = gv[i];
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = vv[i];
+            optim_update<KIND, CLIP>(c, p.x, g.x, m.x, v.x);
+            optim_update<KIND, CLIP>(c, p.y, g.y, m.y, v.y);
+            optim_update<KIND, CLIP>(c, p.z, g.z, m.z, v.z);
+            optim_update<KIND, CLIP>(c, p.w, g.w, m.w, v.w);
+            mv[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) vv[i] = v;
+            pv[i] = p;
+            gv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        const long done = nvec << 2;
+        if (blockIdx.x == 0 && done + t < e.n) {
+            const long i = done + t;
+            float p = e.p[i], m = e.m[i], v = 0.f;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = e.v[i];
+            optim_update<KIND, CLIP>(c, p, e.g[i], m, v);
+            e.m[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) e.v[i] = v;
+            e.p[i] = p;
+            e.g[i] = 0.f;
+        }
+    } else {
+        for (long i = i0; i < e.n; i += stride) {
+            float p = e.p[i], m = e.m[i], v = 0.f;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = e.v[i];
+            optim_update<KIND, CLIP>(c, p, e.g[i], m, v);
+            e.m[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) e.v[i] = v;
+            e.p[i] = p;
+            e.g[i] = 0.f;
+        }
+    }
+}
+
+// (every table entry of an AdamW step needs a second-moment pointer; the table lives on the device, so the caller says
+// whether it filled them in: ledn_optim_desc.has_v)
+int optim_step_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d,
+                    hipStream_t s) {
+    LEDN_REQUIRE(table_dev && d && n_tensors > 0 && max_n > 0);
+    LEDN_REQUIRE(d->kind == LEDN_OPTIM_SGD || d->kind == LEDN_OPTIM_ADAMW);
+    if (d->kind == LEDN_OPTIM_ADAMW) {
+        LEDN_REQUIRE(d->has_v);
+        LEDN_REQUIRE(d->beta1 >= 0.0 && d->beta1 < 1.0 && d->beta2 >= 0.0 && d->beta2 < 1.0 && d->eps > 0.f);
+        LEDN_REQUIRE(d->sched_dev || (d->bc1 > 0.f && d->sqrt_bc2 > 0.f));
+    }
+    int clip = OPT_CLIP_OFF;
+    if (d->clip == LEDN_CLIP_NORM) {
+        LEDN_REQUIRE(d->norm_type == LEDN_NORM_L2 || d->norm_type == LEDN_NORM_INF);
+        LEDN_REQUIRE(d->partials && d->n_partials >= 1 && d->n_partials <= LEDN_CLIP_MAX_PARTIALS && d->max_norm > 0.f);
+        clip = d->norm_type == LEDN_NORM_L2 ? OPT_CLIP_L2 : OPT_CLIP_INF;
+    } else if (d->clip == LEDN_CLIP_VALUE) {
+        LEDN_REQUIRE(d->clip_value > 0.f);
+        clip = OPT_CLIP_VALUE;
+    } else {
+        LEDN_REQUIRE(d->clip == LEDN_CLIP_OFF);
+    }
+    OptimArgs a;
+    a.table = table_dev;
+    a.sched_dev = d->sched_dev;
+    a.A = d->lr_a, a.B = d->lr_b, a.bc1 = d->bc1, a.sbc2 = d->sqrt_bc2;
+    a.momentum = d->momentum;
+    a.b1 = (float)d->beta1, a.omb1 = (float)(1.0 - d->beta1);       // (torch: 1 - beta in double, then to the tensor's type)
+    a.b2 = (float)d->beta2, a.omb2 = (float)(1.0 - d->beta2);
+    a.eps = d->eps;
+    a.weight_decay = d->weight_decay, a.gscale = d->grad_scale;
+    a.partials = d->partials, a.n_partials = d->n_partials;
+    a.max_norm = d->max_norm, a.clip_value = d->clip_value;
+    a.norm_out = d->norm_out;
+    long chunks = cdiv(max_n, 256 * 8);
+    if (chunks > 64) chunks = 64;
+    const dim3 grid((unsigned)chunks, (unsigned)n_tensors);
+#define LEDN_OPTIM(KIND, CLIP) LEDN_LAUNCH((optim_kernel<KIND, CLIP>), grid, dim3(256), 0, s, a)
+#define LEDN_OPTIM_KIND(KIND)                                        \
+    switch (clip) {                                                  \
+        case OPT_CLIP_L2: LEDN_OPTIM(KIND, OPT_CLIP_L2); break;      \
+        case OPT_CLIP_INF: LEDN_OPTIM(KIND, OPT_CLIP_INF); break;    \
+        case OPT_CLIP_VALUE: LEDN_OPTIM(KIND, OPT_CLIP_VALUE); break;\
+        default: LEDN_OPTIM(KIND, OPT_CLIP_OFF); break;              \
+    }
+    if (d->kind == LEDN_OPTIM_SGD) { LEDN_OPTIM_KIND(LEDN_OPTIM_SGD) } else { LEDN_OPTIM_KIND(LEDN_OPTIM_ADAMW) }
+#undef LEDN_OPTIM_KIND
+#undef LEDN_OPTIM
+    return check_launch();
+}
+
 }  // namespace ledn

@@ -138,6 +138,7 @@ int grad_norm_partials_impl(const float* g, long long n, int norm_type, float* p
 int sgd_step_clip_impl(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr, const float* lr_dev,
                        float momentum, float weight_decay, float grad_scale, const float* partials, int n_partials,
                        int norm_type, float max_norm, float clip_value, float* norm_out, hipStream_t s);
+int optim_step_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d, hipStream_t s);
 }  // namespace ledn
 
 #include <mutex>
@@ -598,6 +599,10 @@ int ledn_sgd_step_clip(const ledn_sgd_entry* table_dev, int n_tensors, long long
                        float* norm_out, void* stream) {
     return sgd_step_clip_impl(table_dev, n_tensors, max_n, lr, lr_dev, momentum, weight_decay, grad_scale, partials,
                               n_partials, norm_type, max_norm, clip_value, norm_out, S(stream));
+}
+int ledn_optim_step(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d,
+                    void* stream) {
+    return optim_step_impl(table_dev, n_tensors, max_n, d, S(stream));
 }
 
 }  // extern "C"

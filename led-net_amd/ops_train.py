@@ -1,6 +1,7 @@
 """Tensor-level wrappers for the backward / loss / optimizer entry points of the
 C ABI (second half of include/ledn.h).  Same conventions as ops.py."""
 import ctypes as C
+import math
 
 import torch
 
@@ -778,6 +779,71 @@ class SgdTable:
              momentum, weight_decay, grad_scale, _p(clip.partials) if by_norm else None, clip.n_partials, clip.norm_type,
              float(clip.max_norm), float(clip.clip_value), _p(clip.norm_out) if by_norm else None,
              work=work and (work[0] + ' clip', work[1], 0, 'sgd_clip_kernel'))
+
+
+def optim_scalars(lr_a, lr_b=0.0, betas=(0.9, 0.999), t=1):
+    """the four per-step scalars of ledn_optim_step, {A, B, bc1, sqrt(bc2)}, formed in double as torch.optim.AdamW forms
+    its bias corrections (t: the 1-based step count)"""
+    return (float(lr_a), float(lr_b), 1.0 - float(betas[0]) ** int(t), math.sqrt(1.0 - float(betas[1]) ** int(t)))
+
+
+class OptimTable:
+    """Device table of {param, grad, m, v, n, lr_mult, wd_mult} for ledn_optim_step: SGD (vs=None) or AdamW (vs = the
+    second moments, moms = the first) with one learning-rate and one weight-decay multiplier per tensor."""
+
+    def __init__(self, params, grads, moms, vs=None, lr_mults=None, wd_mults=None):
+        lib = _lib.get_lib()
+        n = len(params)
+        lr_mults = [1.0] * n if lr_mults is None else list(lr_mults)
+        wd_mults = [1.0] * n if wd_mults is None else list(wd_mults)
+        if not (len(grads) == len(moms) == len(lr_mults) == len(wd_mults) == n and (vs is None or len(vs) == n)) or n == 0:
+            raise LednError('OptimTable: one gradient, state and multiplier per parameter')
+        host = (_lib.OptimEntry * n)()
+        self.max_n = 0
+        for i, (p, g, m) in enumerate(zip(params, grads, moms)):
+            ts = (p, g, m) + ((vs[i],) if vs is not None else ())
+            for t in ts:
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+                    raise LednError('optimizer tensors must be contiguous float32 of the parameter\'s size')
+            _check(lib, *ts)
+            host[i].p, host[i].g, host[i].m, host[i].n = p.data_ptr(), g.data_ptr(), m.data_ptr(), p.numel()
+            host[i].v = vs[i].data_ptr() if vs is not None else None
+            host[i].lr_mult, host[i].wd_mult = float(lr_mults[i]), float(wd_mults[i])
+            self.max_n = max(self.max_n, p.numel())
+        self.table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(params[0].device)
+        self.n = n
+        self.ref = params[0]
+        self.has_v = vs is not None
+        self.keep = (params, grads, moms, vs)
+        self.lr_mults, self.wd_mults = lr_mults, wd_mults
+
+    def step(self, kind, lr_a, lr_b=0.0, *, momentum=0.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0,
+             t=1, sched_dev=None, clip=None):
+        """one launch.  kind: _lib.OPTIM_SGD / OPTIM_ADAMW; tensor i moves at lr_mults[i] * lr_a + lr_b with the decay
+        wd_mults[i] * weight_decay; t: AdamW's 1-based step count; sched_dev: None or the four device floats
+        optim_scalars() describes (they then replace lr_a, lr_b and t); clip: as SgdTable.step."""
+        lib = _lib.get_lib()
+        d = _lib.OptimDesc()
+        d.kind, d.has_v = int(kind), int(self.has_v)
+        d.lr_a, d.lr_b, d.bc1, d.sqrt_bc2 = optim_scalars(lr_a, lr_b, betas, t)
+        if sched_dev is not None:
+            if sched_dev.dtype != torch.float32 or sched_dev.numel() != 4:
+                raise LednError('sched_dev: four float32 values {A, B, bc1, sqrt(bc2)}')
+            _check(lib, sched_dev)
+        d.sched_dev = _p(sched_dev)
+        d.momentum, d.eps, d.beta1, d.beta2 = momentum, eps, betas[0], betas[1]
+        d.weight_decay, d.grad_scale = weight_decay, grad_scale
+        d.clip = _lib.CLIP_OFF
+        if clip is not None:
+            _check(lib, clip.buf)
+            by_norm = clip.norm_type != _lib.NORM_NONE
+            d.clip, d.norm_type = (_lib.CLIP_NORM if by_norm else _lib.CLIP_VALUE), clip.norm_type
+            d.partials, d.n_partials = (_p(clip.partials) if by_norm else None), clip.n_partials
+            d.max_norm, d.clip_value = clip.max_norm, clip.clip_value
+            d.norm_out = _p(clip.norm_out) if by_norm else None
+        nel = sum(p.numel() for p in self.keep[0])
+        work = _ops._TIMING is not None and (f'optim {self.n} tensors', (32 if self.has_v else 16) * nel, 0, 'optim_kernel')
+        _run(lib, 'ledn_optim_step', self.ref, self.table.data_ptr(), self.n, self.max_n, C.byref(d), work=work)
 
 
 def norm_partials_count(n):

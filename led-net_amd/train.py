@@ -17,6 +17,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib, ops, ops_train as T
+from . import optim as O
 from .ops import ACT_NONE, ACT_PRELU, ACT_RELU, ACT_RELU6, RES_ADD, RES_GATE, RES_NONE
 
 from ._env import knob_int as _knob_int  # noqa: E402
@@ -1415,7 +1416,7 @@ def led_head_loss(h, inputs, batch_data_samples):
 
 
 # --------------------------------------------------------------------------- #
-# Trainer: SGD(momentum, wd) + PolyLR + data-parallel gradient all-reduce
+# Trainer: SGD(momentum, wd) or AdamW + the config's scheduler list + data-parallel gradient all-reduce
 # --------------------------------------------------------------------------- #
 def parse_clip_grad(clip_grad):
     """mmengine OptimWrapper's ``clip_grad`` -> None or ('norm', norm_type, max_norm) / ('value', clip_value):
@@ -1468,38 +1469,56 @@ class Trainer:
 
     def __init__(self, model, cfg=None, world_size=1, lr=None, momentum=None, weight_decay=None,
                  max_iters=None, power=0.9, eta_min=0.0, bucket_mb=2.0, direct_grads=True, collectives=None,
-                 clip_grad=None):
-        opt = dict((cfg or {}).get('optimizer', {}))
-        if clip_grad is None:       # config: optim_wrapper = dict(type='OptimWrapper', optimizer=..., clip_grad=...)
-            clip_grad = ((cfg or {}).get('optim_wrapper') or {}).get('clip_grad')
+                 clip_grad=None, paramwise_cfg=None):
+        # config: optim_wrapper = dict(type='OptimWrapper', optimizer=..., clip_grad=..., paramwise_cfg=...); a config
+        # without that section keeps its optimizer at the top level.  (optim.py / DESIGN.md "Optimizer construction
+        # from the config": every key is honoured or raises ValueError.)
+        wrapper = (cfg or {}).get('optim_wrapper') or {}
+        opt_cfg = wrapper.get('optimizer') if wrapper.get('optimizer') is not None else (cfg or {}).get('optimizer', {})
+        opt = O.parse_optimizer(opt_cfg, lr, momentum, weight_decay)
+        if clip_grad is None:
+            clip_grad = wrapper.get('clip_grad')
         clip = parse_clip_grad(clip_grad)
+        pw = O.parse_paramwise(paramwise_cfg if paramwise_cfg is not None else wrapper.get('paramwise_cfg'))
         self.model = model
-        self.base_lr = lr if lr is not None else opt.get('lr', 0.01)
-        self.momentum = momentum if momentum is not None else opt.get('momentum', 0.9)
-        self.wd = weight_decay if weight_decay is not None else opt.get('weight_decay', 5e-4)
-        sched = ((cfg or {}).get('param_scheduler') or [dict(power=0.9, eta_min=0, end=80000)])[0]
-        self.max_iters = max_iters or sched.get('end', 80000)
-        self.power, self.eta_min = sched.get('power', power), sched.get('eta_min', eta_min)
+        self.opt_kind = opt['kind']
+        self.base_lr, self.wd = opt['lr'], opt['weight_decay']
+        self.momentum = opt.get('momentum', 0.0)
+        self.betas, self.eps = opt.get('betas', (0.9, 0.999)), opt.get('eps', 1e-8)
+        self.sched = O.Schedule((cfg or {}).get('param_scheduler') or None, max_iters, power, eta_min)
+        self.max_iters = max_iters or self.sched.end
+        first = self.sched.entries[0]       # (a lone PolyLR: the two numbers older callers read)
+        self.power, self.eta_min = first.get('power', power), first.get('eta_min', eta_min)
+        self.paramwise = pw
+        # plain SGD under a lone PolyLR keeps the ledn_sgd_step(_clip) launch; everything else -- AdamW, per-parameter
+        # multipliers, a scheduler list -- is ONE ledn_optim_step launch over the extended table
+        self._general = not (self.opt_kind == 'SGD' and pw is None and self.sched.lone_poly)
         self.iter = 0
         self.world = world_size
         # gradient layout: [stem | everything else], each in module order.  The stem's backward comes LAST (and is
         # the long high-resolution part): when it starts, every other parameter gradient is complete
         # (GradReadyFn 'post_stem') and that tail of the buffer is all-reduced while the stem's backward runs.
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
-        late = [p for n, p in named if n.startswith('backbone.stem.')]
-        early = [p for n, p in named if not n.startswith('backbone.stem.')]
-        self.params = late + early
+        late = [(n, p) for n, p in named if n.startswith('backbone.stem.')]
+        early = [(n, p) for n, p in named if not n.startswith('backbone.stem.')]
+        self.params = [p for _, p in late] + [p for _, p in early]
         dev = self.params[0].device
         n = sum(p.numel() for p in self.params)
-        self.n_late = sum(p.numel() for p in late)
+        self.n_late = sum(p.numel() for _, p in late)
         self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.flat_mom = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.views, self.moms, off = [], [], 0
+        self.flat_mom = torch.zeros(n, dtype=torch.float32, device=dev)      # (AdamW: exp_avg)
+        self.flat_v = torch.zeros(n, dtype=torch.float32, device=dev) if self.opt_kind == 'AdamW' else None   # exp_avg_sq
+        self.views, self.moms, self.vs, off = [], [], [], 0
         for p in self.params:
             k = p.numel()
             self.views.append(self.flat_grad[off:off + k].view_as(p))
             self.moms.append(self.flat_mom[off:off + k].view_as(p))
+            if self.flat_v is not None:
+                self.vs.append(self.flat_v[off:off + k].view_as(p))
             off += k
+        mults = O.paramwise_multipliers(model, pw) if pw is not None else {}
+        self.names = [n_ for n_, _ in late] + [n_ for n_, _ in early]
+        self.mults = [mults.get(name, (1.0, 1.0)) for name in self.names]      # (lr_mult, decay_mult) per parameter
         self.table = None
         # gradient clipping: the norm pass over flat_grad writes its per-workgroup partials into the trainer's own
         # persistent buffer [partials | total_norm | coef]; the SGD launch combines them in its prologue
@@ -1584,43 +1603,116 @@ class Trainer:
     # resume: what mmengine's CheckpointHook stores besides the weights (`optimizer` = OptimWrapper.state_dict() =
     # torch.optim.SGD.state_dict() over model.parameters() order, `param_schedulers` = [PolyLR.state_dict()])
     def optimizer_state_dict(self):
-        """torch.optim.SGD-format state: parameter index = position in ``model.parameters()``; a momentum
-        buffer only for parameters that have received a gradient (SGD creates its state lazily)."""
+        """torch.optim.SGD / torch.optim.AdamW-format state: parameter index = position in ``model.parameters()``;
+        state only for parameters that have received a gradient (torch creates its state lazily): SGD
+        {'momentum_buffer'}, AdamW {'step', 'exp_avg', 'exp_avg_sq'}.  One param group; with a paramwise_cfg one group
+        per parameter with its own lr / weight_decay / initial_lr, as mmengine's constructor builds them."""
         order = list(self.model.parameters())
         pos = {id(p): i for i, p in enumerate(self.params)}
         live = {id(p) for p in getattr(self, 'live', [])} if self.table is not None else set()
         state = {}
         for i, p in enumerate(order):
-            if id(p) in live:
-                state[i] = {'momentum_buffer': self.moms[pos[id(p)]].detach().clone().cpu()}
-        group = dict(lr=self.lr(), momentum=self.momentum, dampening=0, weight_decay=self.wd, nesterov=False,
-                     maximize=False, foreach=None, differentiable=False, fused=None, initial_lr=self.base_lr,
-                     params=list(range(len(order))))
-        return {'state': state, 'param_groups': [group]}
+            if id(p) not in live:
+                continue
+            k = pos[id(p)]
+            if self.opt_kind == 'AdamW':
+                state[i] = {'step': torch.tensor(float(self.iter), dtype=torch.float32),
+                            'exp_avg': self.moms[k].detach().clone().cpu(),
+                            'exp_avg_sq': self.vs[k].detach().clone().cpu()}
+            else:
+                state[i] = {'momentum_buffer': self.moms[k].detach().clone().cpu()}
+
+        def group(lr_mult, decay_mult, params):
+            if self.opt_kind == 'AdamW':
+                g = dict(lr=self._group_lr(lr_mult), betas=tuple(self.betas), eps=self.eps,
+                         weight_decay=self.wd * decay_mult, amsgrad=False, maximize=False, foreach=None, capturable=False,
+                         differentiable=False, fused=None)
+            else:
+                g = dict(lr=self._group_lr(lr_mult), momentum=self.momentum, dampening=0, weight_decay=self.wd * decay_mult,
+                         nesterov=False, maximize=False, foreach=None, differentiable=False, fused=None)
+            g.update(initial_lr=self.base_lr * lr_mult, params=params)
+            return g
+        if self.paramwise is None:
+            return {'state': state, 'param_groups': [group(1.0, 1.0, list(range(len(order))))]}
+        return {'state': state, 'param_groups': [group(*(self.mults[pos[id(p)]] if id(p) in pos else (1.0, 1.0)), [i])
+                                                 for i, p in enumerate(order)]}
+
+    def _group_lr(self, lr_mult):
+        if lr_mult == 1.0:
+            return self.lr()
+        a, b = self.sched.scalars(self.base_lr, self.iter)
+        return lr_mult * a + b
 
     def scheduler_state_dict(self):
-        return {'last_step': self.iter, 'begin': 0, 'end': self.max_iters, 'power': self.power, 'eta_min': self.eta_min,
-                'total_iters': self.max_iters, 'base_values': [self.base_lr], 'by_epoch': False}
+        return self.scheduler_state_dicts()[0]
+
+    def scheduler_state_dicts(self):
+        """one dict per entry of the config's param_scheduler list (the mmengine schedulers' state_dict() fields)"""
+        if self.sched.lone_poly:
+            return [{'last_step': self.iter, 'begin': 0, 'end': self.max_iters, 'power': self.power, 'eta_min': self.eta_min,
+                     'total_iters': self.max_iters, 'base_values': [self.base_lr], 'by_epoch': False}]
+        if self.paramwise is None:
+            base = [self.base_lr]
+        else:
+            pos = {id(p): i for i, p in enumerate(self.params)}
+            base = [self.base_lr * (self.mults[pos[id(p)]][0] if id(p) in pos else 1.0) for p in self.model.parameters()]
+        return self.sched.state_dicts(base, self.iter)
 
     def load_optimizer_state_dict(self, opt_sd, schedulers=None, iter=None):
-        """restore the momentum buffers (and the schedule position) saved by optimizer_state_dict /
-        an mmengine checkpoint of the same model"""
+        """restore the optimizer state (SGD: momentum buffers; AdamW: both moments and the step count) and the schedule
+        position saved by optimizer_state_dict / an mmengine checkpoint of the same model.  A checkpoint of the other
+        optimizer raises ValueError."""
         order = list(self.model.parameters())
         pos = {id(p): i for i, p in enumerate(self.params)}
-        for i, st in opt_sd.get('state', {}).items():
+        states = opt_sd.get('state', {})
+        groups = opt_sd.get('param_groups') or [{}]
+        saved = None
+        if any('exp_avg' in st for st in states.values()) or 'betas' in groups[0]:
+            saved = 'AdamW'
+        elif any('momentum_buffer' in st for st in states.values()) or 'momentum' in groups[0]:
+            saved = 'SGD'
+        if saved is not None and saved != self.opt_kind:
+            raise ValueError(f'the checkpoint holds {saved} optimizer state, this trainer runs {self.opt_kind}')
+        step = None
+        for i, st in states.items():
             p = order[int(i)]
-            buf = st.get('momentum_buffer')
-            if buf is not None and id(p) in pos:
-                self.moms[pos[id(p)]].copy_(buf.to(self.flat_mom.device, torch.float32).view_as(p))
+            if id(p) not in pos:
+                continue
+            k = pos[id(p)]
+            if self.opt_kind == 'AdamW':
+                if st.get('exp_avg') is not None:
+                    self.moms[k].copy_(st['exp_avg'].to(self.flat_mom.device, torch.float32).view_as(p))
+                    self.vs[k].copy_(st['exp_avg_sq'].to(self.flat_v.device, torch.float32).view_as(p))
+                    step = int(float(st.get('step', 0))) if step is None else step
+            else:
+                buf = st.get('momentum_buffer')
+                if buf is not None:
+                    self.moms[k].copy_(buf.to(self.flat_mom.device, torch.float32).view_as(p))
+        if step is not None:
+            self.iter = step            # (AdamW's step count IS the iteration counter: mmengine steps both together)
         if schedulers:
             self.iter = int(schedulers[0].get('last_step', self.iter))
         if iter is not None:
             self.iter = int(iter)
 
     def lr(self):
-        """mmengine PolyLR (by iteration): (base-eta_min)*(1-it/max)^power + eta_min."""
-        t = min(self.iter, self.max_iters) / self.max_iters
-        return (self.base_lr - self.eta_min) * (1.0 - t) ** self.power + self.eta_min
+        """the base group's learning rate at this iteration (optim.Schedule; a lone mmengine PolyLR by iteration:
+        (base-eta_min)*(1-it/max)^power + eta_min)."""
+        return self.sched.value(self.base_lr, self.iter)
+
+    def _optim_scalars(self):
+        """{A, B, bc1, sqrt(bc2)} of this iteration for ledn_optim_step (AdamW's 1-based step count = iter + 1)"""
+        a, b = self.sched.scalars(self.base_lr, self.iter)
+        return T.optim_scalars(a, b, self.betas, self.iter + 1)
+
+    def _refresh_dev(self):
+        """the device-resident scalars a captured graph reads: the rate (plain SGD) or {A, B, bc1, sqrt(bc2)}"""
+        if not self._general:
+            self._lr_dev.fill_(self.lr())
+            return
+        vals = self._optim_scalars()
+        for i in range(4 if self.opt_kind == 'AdamW' else 2):
+            self._lr_dev[i].fill_(vals[i])
 
     def _attach_grads(self):
         for p, v in zip(self.live, self.live_views):
@@ -1751,7 +1843,12 @@ class Trainer:
             for p, v in zip(self.live, self.live_views):
                 v.copy_(p.grad)
             self._attach_grads()
-            self.table = T.SgdTable(self.live, self.live_views, [self.moms[i] for i in idx])
+            if self._general:
+                self.table = T.OptimTable(self.live, self.live_views, [self.moms[i] for i in idx],
+                                          [self.vs[i] for i in idx] if self.flat_v is not None else None,
+                                          [self.mults[i][0] for i in idx], [self.mults[i][1] for i in idx])
+            else:
+                self.table = T.SgdTable(self.live, self.live_views, [self.moms[i] for i in idx])
             if self.direct_grads:
                 self._sink_map = {id(p): v for p, v in zip(self.live, self.live_views)}
             if _Packs.entries:
@@ -1782,12 +1879,18 @@ class Trainer:
             if self._gstream is not None:
                 torch.cuda.current_stream(self.flat_grad.device).wait_stream(self._gstream)
         if self._lr_dev is not None and not torch.cuda.is_current_stream_capturing():
-            self._lr_dev.fill_(self.lr())       # eager step after a capture(): keep the device-resident rate current
-        if self.clip is None:
-            self.table.step(self.lr(), self.momentum, self.wd, 1.0 / self.world, lr_dev=self._lr_dev)
-        else:
+            self._refresh_dev()                 # eager step after a capture(): keep the device-resident rate current
+        if self.clip is not None:
             # after the exchange (and the wait for its stream): the norm of the all-reduced gradient, the same on every rank
             self.clip.norm_pass(self.flat_grad)
+        if self._general:
+            a, b, _, _ = self._optim_scalars()
+            self.table.step(_lib.OPTIM_ADAMW if self.opt_kind == 'AdamW' else _lib.OPTIM_SGD, a, b, momentum=self.momentum,
+                            betas=self.betas, eps=self.eps, weight_decay=self.wd, grad_scale=1.0 / self.world,
+                            t=self.iter + 1, sched_dev=self._lr_dev, clip=self.clip)
+        elif self.clip is None:
+            self.table.step(self.lr(), self.momentum, self.wd, 1.0 / self.world, lr_dev=self._lr_dev)
+        else:
             self.table.step(self.lr(), self.momentum, self.wd, 1.0 / self.world, lr_dev=self._lr_dev, clip=self.clip)
         self.iter += 1
         # detached: a caller holding the returned losses would otherwise keep the step's autograd graph
@@ -1820,7 +1923,7 @@ class Trainer:
         from .segmentor import SegDataSample
         self._static_samples = [SegDataSample(gt=self._static_lab[i], metainfo=dict(getattr(ds, 'metainfo', {}) or {}))
                                 for i, ds in enumerate(data_samples)]
-        self._lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._lr_dev = torch.zeros(4 if self._general else 1, dtype=torch.float32, device=dev)
         self._valid_host = None         # (a second capture() starts from the new batch's padding extents)
         if inputs.dtype == torch.uint8 and getattr(self.model, 'pre_scale', None) is not None:
             # per-image valid extents (batch padding) live in a resident buffer the graph reads: replay() refreshes it
@@ -1829,23 +1932,26 @@ class Trainer:
         snap = None
         if restore:
             snap = ([p.detach().clone() for p in self.params], self.flat_mom.clone(),
-                    [b.detach().clone() for b in self.model.buffers()], self.iter)
+                    [b.detach().clone() for b in self.model.buffers()], self.iter,
+                    self.flat_v.clone() if self.flat_v is not None else None)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(warmup, 2 if self.table is None else 0)):     # (the sinks attach in the second step)
-                self._lr_dev.fill_(self.lr())
+                self._refresh_dev()
                 self.train_step(self._static_in, self._static_samples)
             if snap is not None:
                 with torch.no_grad():
                     for p, v in zip(self.params, snap[0]):
                         p.copy_(v)
                     self.flat_mom.copy_(snap[1])
+                    if self.flat_v is not None:
+                        self.flat_v.copy_(snap[4])
                     for b, v in zip(self.model.buffers(), snap[2]):
                         b.copy_(v)
                 self.iter = snap[3]
         torch.cuda.current_stream(dev).wait_stream(side)
-        self._lr_dev.fill_(self.lr())
+        self._refresh_dev()
         self._graph = torch.cuda.CUDAGraph()
         # N > 1: other threads of the process (ProcessGroupNCCL's watchdog) keep calling the runtime while this
         # thread captures; 'thread_local' confines the capture-safety checks to the capturing thread
@@ -1877,7 +1983,7 @@ class Trainer:
                 if getattr(self, '_valid_host', None) is None or not torch.equal(ext, self._valid_host):
                     self._valid_host = ext
                     self.model._valid_static.copy_(ext.to(self.model._valid_static.device))
-        self._lr_dev.fill_(self.lr())
+        self._refresh_dev()
         self._graph.replay()
         self.iter += 1
         return self._static_out
