@@ -791,6 +791,61 @@ int ledn_ohem2_up_w_bwd(const float* src0, const float* src1, int N, int Hs, int
                         float* dsrc0, float* dsrc1, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * CrossEntropyLoss (softmax form, mmseg/models/losses/cross_entropy_loss.py:12-78) and DiceLoss (dice_loss.py:11-91,
+ * 141-188) for LEDHead.loss_by_feat.  Two families each, like ledn_ohem_ce_* / ledn_ohem_ce_up_*:
+ *   generic        logits [N][HW][C] f32 (NHWC), target [N][HW] int64, C > 1
+ *   resize-folded  src [N,Hs,Ws,2] f32, target [N,H,W] with H = 2 Hs, W = 2 Ws: the loss of the exact 2x bilinear
+ *                  (align_corners=False) resize of src, never materialised; the backward writes dsrc [N,Hs,Ws,2]
+ *                  through the adjoint of that resize.  Any even H, W (a W % 4 == 2 row ends in a two-pixel tail).
+ * A forward is one streaming pass (per-workgroup partial sums) and a single-workgroup finish that adds them in a fixed
+ * order: no float atomics, bit-reproducible.  Nothing per-pixel is stored: work holds ledn_seg_loss_work_floats(N)
+ * floats (O(workgroups + N)), and the backward re-forms the probabilities from the logits.  N*HW < 2^31, N <= 65535.
+ *   out[0]  the loss, loss_weight applied
+ *   out[1]  top-1 accuracy in percent as ledn_ohem_ce_fwd's out[1]: first-max argmax over the pixels whose label is
+ *           not ignore_index (Dice: acc_ignore_index, which takes no other part in that loss)
+ *   out[2], out[3]  CE: the divisor and the number of pixels in the loss; Dice: 0, 0
+ * reduction: 0 = 'mean', 1 = 'sum'.
+ * CE: per pixel w[y] * CE (class_weight [C] f32 on the device or NULL); pixels with label == ignore_index (or outside
+ * [0, C)) contribute nothing.  'mean' divides by avg_factor + FLT_EPSILON (losses/utils.py:75-79), avg_factor = N*HW,
+ * or the number of pixels in the loss (avg_non_ignore != 0), or with class weights the sum of w[y] over them; 'sum'
+ * uses no divisor.  No pixel in the loss: loss 0 and a zero gradient.
+ *   dlogits[p][c] = dloss * loss_weight / divisor * w[y_p] * (softmax_c - onehot_c)
+ * Dice: p = sigmoid(z) per class (use_sigmoid != 0) or softmax over the classes; one-hot target of clamp(label, 0, C)
+ * with row C dropped, so a label >= C (255) has target 0 everywhere and still adds its p to the denominator, a
+ * negative label is class 0.  ignore_class in [0, C) removes that class channel from all three sums.  Per image n:
+ *   a = sum p t, b = sum p^2, c = sum t^2, loss_n = 1 - 2a / ((b + eps) + (c + eps))       (naive_dice == 0)
+ *   a = sum p t, b = sum p,   c = sum t,   loss_n = 1 - (2a + eps) / (b + c + eps)         (naive_dice != 0)
+ * out[0] = loss_weight * mean_n or sum_n of loss_n; work[4 n .. 4 n + 3] = a, b, c (without eps), loss_n.
+ *   dL/dp = -2 t / D + 4 a p / D^2   resp.   -2 t / D + (2a + eps) / D^2   (D the denominator above), pulled through the
+ *   sigmoid / softmax Jacobian and scaled by loss_weight * dloss (/ N for 'mean'). */
+long long ledn_seg_loss_work_floats(long long N);
+int ledn_ce_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C,
+                     const float* class_weight, int ignore_index, int reduction, int avg_non_ignore, float loss_weight,
+                     float* work, float* out, void* stream);
+int ledn_ce_loss_bwd(const float* logits, const long long* target, int N, long long HW, int C,
+                     const float* class_weight, int ignore_index, float loss_weight, const float* work,
+                     const float* out, const float* dloss, float* dlogits, void* stream);
+int ledn_ce_loss_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                        const float* class_weight, int ignore_index, int reduction, int avg_non_ignore,
+                        float loss_weight, float* work, float* out, void* stream);
+int ledn_ce_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                        const float* class_weight, int ignore_index, float loss_weight, const float* work,
+                        const float* out, const float* dloss, float* dsrc, void* stream);
+int ledn_dice_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C, int use_sigmoid,
+                       int naive_dice, int ignore_class, int acc_ignore_index, int reduction, float eps,
+                       float loss_weight, float* work, float* out, void* stream);
+int ledn_dice_loss_bwd(const float* logits, const long long* target, int N, long long HW, int C, int use_sigmoid,
+                       int naive_dice, int ignore_class, int reduction, float eps, float loss_weight,
+                       const float* work, const float* out, const float* dloss, float* dlogits, void* stream);
+int ledn_dice_loss_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                          int use_sigmoid, int naive_dice, int ignore_class, int acc_ignore_index, int reduction,
+                          float eps, float loss_weight, float* work, float* out, void* stream);
+int ledn_dice_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                          int use_sigmoid, int naive_dice, int ignore_class, int reduction, float eps,
+                          float loss_weight, const float* work, const float* out, const float* dloss, float* dsrc,
+                          void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The four pooled-context MLPs of Muti_AFF (classification/model_utils.py:377-400: AdaptiveAvgPool2d(S) ->
  * Conv1x1(C->Ci)+bias -> BatchNorm -> ReLU -> Conv1x1(Ci->C)+bias -> [BatchNorm: in the gate kernel], S = 4, 8, 16, 1)
  * as ONE launch sequence for all four scales: they are chains of tiny launch-bound kernels (~50 launches per

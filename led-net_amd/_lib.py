@@ -220,6 +220,16 @@ _PROTOS = {
                              fp, fp, fp, fp, vp], i32),
     'ledn_ohem2_up_w_bwd': ([fp, fp, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, C.c_float, C.c_float, fp, fp, fp, fp,
                              vp], i32),
+    # CrossEntropyLoss / DiceLoss (seg_loss.hip): generic and resize-folded, forward and backward
+    'ledn_seg_loss_work_floats': ([i64], i64),
+    'ledn_ce_loss_fwd': ([fp, vp, i32, i64, i32, fp, i32, i32, i32, C.c_float, fp, fp, vp], i32),
+    'ledn_ce_loss_bwd': ([fp, vp, i32, i64, i32, fp, i32, C.c_float, fp, fp, fp, fp, vp], i32),
+    'ledn_ce_loss_up_fwd': ([fp, i32, i32, i32, i32, i32, vp, fp, i32, i32, i32, C.c_float, fp, fp, vp], i32),
+    'ledn_ce_loss_up_bwd': ([fp, i32, i32, i32, i32, i32, vp, fp, i32, C.c_float, fp, fp, fp, fp, vp], i32),
+    'ledn_dice_loss_fwd': ([fp, vp, i32, i64, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, fp, fp, vp], i32),
+    'ledn_dice_loss_bwd': ([fp, vp, i32, i64, i32, i32, i32, i32, i32, C.c_float, C.c_float, fp, fp, fp, fp, vp], i32),
+    'ledn_dice_loss_up_fwd': ([fp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, fp, fp, vp], i32),
+    'ledn_dice_loss_up_bwd': ([fp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, C.c_float, C.c_float, fp, fp, fp, fp, vp], i32),
     'ledn_sgd_step': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, vp], i32),
     'ledn_grad_norm_partials': ([fp, i64, i32, fp, i32, vp], i32),
     'ledn_sgd_step_clip': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, fp, i32, i32, C.c_float, C.c_float,

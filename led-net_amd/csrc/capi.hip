@@ -127,6 +127,16 @@ int ohem_ce_up_bwd_impl(const float* src, int N, int Hs, int Ws, int H, int W, c
 int ohem_ce_bwd_impl(const float* logits, const long long* target, long long P, int C, int ignore_label,
                      const float* work, const float* out, const float* dloss, float loss_weight,
                      const float* cw, float* dlogits, hipStream_t s);
+long long seg_loss_work_floats(long long N);
+int seg_loss_fwd_impl(int kind, const float* logits, const long long* target, int N, long long HW, int C, const SlCfg& q,
+                      float* work, float* out, hipStream_t s);
+int seg_loss_bwd_impl(int kind, const float* logits, const long long* target, int N, long long HW, int C, const SlCfg& q,
+                      const float* work, const float* out, const float* dloss, float* dlogits, hipStream_t s);
+int seg_loss_up_fwd_impl(int kind, const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                         const SlCfg& q, float* work, float* out, hipStream_t s);
+int seg_loss_up_bwd_impl(int kind, const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                         const SlCfg& q, const float* work, const float* out, const float* dloss, float* dsrc,
+                         hipStream_t s);
 int tta_accumulate_impl(const ledn_tta_desc& d, hipStream_t s);
 int slide_accumulate_impl(float* canvas, const float* crop, int N, int C, int H, int W, int y1, int x1, int hc, int wc,
                           int crop_planar, hipStream_t s);
@@ -584,6 +594,69 @@ int ledn_ohem_ce_w_bwd(const float* logits, const long long* target, long long P
                        const float* class_weight, float* dlogits, void* stream) {
     return ohem_ce_bwd_impl(logits, target, P, C, ignore_label, work, out, dloss, loss_weight, class_weight, dlogits,
                             S(stream));
+}
+static SlCfg sl_ce_cfg(const float* class_weight, int ignore_index, int reduction, int avg_non_ignore, float loss_weight) {
+    SlCfg q = {class_weight, ignore_index, -1, 0, reduction, avg_non_ignore, 0.f, loss_weight};
+    return q;
+}
+static SlCfg sl_dice_cfg(int naive_dice, int ignore_class, int acc_ignore_index, int reduction, float eps, float loss_weight) {
+    SlCfg q = {nullptr, acc_ignore_index, ignore_class, naive_dice != 0, reduction, 0, eps, loss_weight};
+    return q;
+}
+long long ledn_seg_loss_work_floats(long long N) { return seg_loss_work_floats(N); }
+int ledn_ce_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C,
+                     const float* class_weight, int ignore_index, int reduction, int avg_non_ignore, float loss_weight,
+                     float* work, float* out, void* stream) {
+    return seg_loss_fwd_impl(SL_CE, logits, target, N, HW, C,
+                             sl_ce_cfg(class_weight, ignore_index, reduction, avg_non_ignore, loss_weight), work, out, S(stream));
+}
+int ledn_ce_loss_bwd(const float* logits, const long long* target, int N, long long HW, int C,
+                     const float* class_weight, int ignore_index, float loss_weight, const float* work,
+                     const float* out, const float* dloss, float* dlogits, void* stream) {
+    return seg_loss_bwd_impl(SL_CE, logits, target, N, HW, C, sl_ce_cfg(class_weight, ignore_index, 0, 0, loss_weight), work,
+                             out, dloss, dlogits, S(stream));
+}
+int ledn_ce_loss_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                        const float* class_weight, int ignore_index, int reduction, int avg_non_ignore,
+                        float loss_weight, float* work, float* out, void* stream) {
+    return seg_loss_up_fwd_impl(SL_CE, src, N, Hs, Ws, H, W, target,
+                                sl_ce_cfg(class_weight, ignore_index, reduction, avg_non_ignore, loss_weight), work, out,
+                                S(stream));
+}
+int ledn_ce_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                        const float* class_weight, int ignore_index, float loss_weight, const float* work,
+                        const float* out, const float* dloss, float* dsrc, void* stream) {
+    return seg_loss_up_bwd_impl(SL_CE, src, N, Hs, Ws, H, W, target, sl_ce_cfg(class_weight, ignore_index, 0, 0, loss_weight),
+                                work, out, dloss, dsrc, S(stream));
+}
+int ledn_dice_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C, int use_sigmoid,
+                       int naive_dice, int ignore_class, int acc_ignore_index, int reduction, float eps,
+                       float loss_weight, float* work, float* out, void* stream) {
+    return seg_loss_fwd_impl(use_sigmoid ? SL_DICE_SIGMOID : SL_DICE_SOFTMAX, logits, target, N, HW, C,
+                             sl_dice_cfg(naive_dice, ignore_class, acc_ignore_index, reduction, eps, loss_weight), work, out,
+                             S(stream));
+}
+int ledn_dice_loss_bwd(const float* logits, const long long* target, int N, long long HW, int C, int use_sigmoid,
+                       int naive_dice, int ignore_class, int reduction, float eps, float loss_weight,
+                       const float* work, const float* out, const float* dloss, float* dlogits, void* stream) {
+    return seg_loss_bwd_impl(use_sigmoid ? SL_DICE_SIGMOID : SL_DICE_SOFTMAX, logits, target, N, HW, C,
+                             sl_dice_cfg(naive_dice, ignore_class, -1, reduction, eps, loss_weight), work, out, dloss,
+                             dlogits, S(stream));
+}
+int ledn_dice_loss_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                          int use_sigmoid, int naive_dice, int ignore_class, int acc_ignore_index, int reduction,
+                          float eps, float loss_weight, float* work, float* out, void* stream) {
+    return seg_loss_up_fwd_impl(use_sigmoid ? SL_DICE_SIGMOID : SL_DICE_SOFTMAX, src, N, Hs, Ws, H, W, target,
+                                sl_dice_cfg(naive_dice, ignore_class, acc_ignore_index, reduction, eps, loss_weight), work,
+                                out, S(stream));
+}
+int ledn_dice_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                          int use_sigmoid, int naive_dice, int ignore_class, int reduction, float eps,
+                          float loss_weight, const float* work, const float* out, const float* dloss, float* dsrc,
+                          void* stream) {
+    return seg_loss_up_bwd_impl(use_sigmoid ? SL_DICE_SIGMOID : SL_DICE_SOFTMAX, src, N, Hs, Ws, H, W, target,
+                                sl_dice_cfg(naive_dice, ignore_class, -1, reduction, eps, loss_weight), work, out, dloss, dsrc,
+                                S(stream));
 }
 int ledn_sgd_step(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,
                   const float* lr_dev, float momentum, float weight_decay, float grad_scale, void* stream) {

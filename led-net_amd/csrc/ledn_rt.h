@@ -423,6 +423,17 @@ bool head_fwd_supported(const ledn_conv_desc& d);
 int head_fwd(const ledn_conv_desc& d, hipStream_t s);
 int channel_stats_fast(const void* x, const void* xadd, long long P, int C, int dtype, float* sum, float* sqsum,
                        hipStream_t s);
+// seg_loss.hip: the loss of a ledn_ce_loss_* / ledn_dice_loss_* call and its settings
+enum { SL_CE = 0, SL_DICE_SIGMOID = 1, SL_DICE_SOFTMAX = 2 };
+struct SlCfg {
+    const float* cw;        // CE: class weights [C] on the device or null
+    int ignore_index;       // the label that takes no part in the accuracy (CE: nor in the loss)
+    int ignore_class;       // Dice: the dropped class channel (outside [0, C): none)
+    int naive;              // Dice: first powers in the denominator
+    int reduction;          // 0 mean, 1 sum
+    int avg_non_ignore;     // CE
+    float eps, loss_weight;
+};
 
 }  // namespace ledn
 

@@ -606,6 +606,165 @@ def ohem2_up_bwd(src0, src1, hw, work, out, dloss0, dloss1, lw0, lw1, ignore_lab
     return d0, d1
 
 
+# --------------------------------------------------------------------------- #
+# CrossEntropyLoss / DiceLoss (csrc/seg_loss.hip): generic (NHWC logits) and resize-folded (src at half the label size)
+# --------------------------------------------------------------------------- #
+_REDUCTIONS = {'mean': 0, 'sum': 1}
+
+
+def _seg_loss_args(who, logits, target, up, reduction):
+    """the checks shared by the eight wrappers -> (lib, N, shape arguments of the C call, pixel count)"""
+    lib = _lib.get_lib()
+    if reduction not in _REDUCTIONS:
+        raise LednError(f"{who}: reduction={reduction!r} (supported: 'mean' and 'sum')")
+    if logits.dtype != torch.float32 or target.dtype != torch.int64 or logits.dim() != 4:
+        raise LednError(f'{who}: f32 NHWC logits [N,H,W,C] and an int64 target required')
+    N, Hl, Wl, Cc = (int(v) for v in logits.shape)
+    if target.dim() != 3 or target.shape[0] != N or N < 1:
+        raise LednError(f'{who}: target [N,H,W] required')
+    H, W = int(target.shape[1]), int(target.shape[2])
+    if up:
+        if Cc != 2 or H != 2 * Hl or W != 2 * Wl:
+            raise LednError(f'{who}: src [N,Hs,Ws,2] and a target of exactly twice its size required')
+        if target.data_ptr() % 16 or logits.data_ptr() % 8:
+            raise LednError(f'{who}: target must be 16-byte aligned, src 8-byte aligned')
+        return lib, N, (N, Hl, Wl, H, W), N * H * W
+    if Cc < 2 or (H, W) != (Hl, Wl):
+        raise LednError(f'{who}: at least two classes and a target of the logits\' size required')
+    return lib, N, (N, H * W, Cc), N * H * W
+
+
+def _seg_loss_bufs(lib, N, ref):
+    work = torch.empty(lib.cdll.ledn_seg_loss_work_floats(N), dtype=torch.float32, device=ref.device)
+    return work, torch.empty(4, dtype=torch.float32, device=ref.device)
+
+
+def _ce_loss_fwd(who, up, logits, target, class_weight, ignore_index, reduction, avg_non_ignore, loss_weight):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, up, reduction)
+    cw = _class_weight(class_weight, logits, logits.shape[-1], who)
+    work, out = _seg_loss_bufs(lib, N, logits)
+    _check(lib, logits, target, work, out)
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{logits.shape[-1]}', _nb(logits, target), 20 * P * logits.shape[-1],
+                                           'sl_up_fwd_kernel' if up else 'sl_fwd_kernel')
+    if up:
+        _run(lib, 'ledn_ce_loss_up_fwd', logits, _p(logits), *shape, _p(target), _p(cw), int(ignore_index),
+             _REDUCTIONS[reduction], int(bool(avg_non_ignore)), float(loss_weight), _p(work), _p(out), work=timing)
+    else:
+        _run(lib, 'ledn_ce_loss_fwd', logits, _p(logits), _p(target), *shape, _p(cw), int(ignore_index),
+             _REDUCTIONS[reduction], int(bool(avg_non_ignore)), float(loss_weight), _p(work), _p(out), work=timing)
+    return out, work
+
+
+def _ce_loss_bwd(who, up, logits, target, work, out, dloss, class_weight, ignore_index, loss_weight):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, up, 'mean')
+    cw = _class_weight(class_weight, logits, logits.shape[-1], who)
+    dl = torch.empty_like(logits)
+    dloss = dloss.reshape(1).to(torch.float32).contiguous()
+    _check(lib, logits, target, work, out, dloss, dl)
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{logits.shape[-1]}', _nb(logits, target, dl), 20 * P * logits.shape[-1],
+                                           'sl_up_bwd_kernel' if up else 'sl_bwd_kernel')
+    if up:
+        _run(lib, 'ledn_ce_loss_up_bwd', logits, _p(logits), *shape, _p(target), _p(cw), int(ignore_index),
+             float(loss_weight), _p(work), _p(out), _p(dloss), _p(dl), work=timing)
+    else:
+        _run(lib, 'ledn_ce_loss_bwd', logits, _p(logits), _p(target), *shape, _p(cw), int(ignore_index),
+             float(loss_weight), _p(work), _p(out), _p(dloss), _p(dl), work=timing)
+    return dl
+
+
+def ce_loss_fwd(logits, target, loss_weight=1.0, ignore_index=255, class_weight=None, reduction='mean',
+                avg_non_ignore=False):
+    """CrossEntropyLoss (softmax form): logits [N,H,W,C] f32, target [N,H,W] int64 -> (out[4] = loss, acc, divisor,
+    #pixels in the loss ; work).  class_weight: None or [C] f32 on the device."""
+    return _ce_loss_fwd('ce_loss', False, logits, target, class_weight, ignore_index, reduction, avg_non_ignore, loss_weight)
+
+
+def ce_loss_bwd(logits, target, work, out, dloss, loss_weight=1.0, ignore_index=255, class_weight=None):
+    return _ce_loss_bwd('ce_loss_bwd', False, logits, target, work, out, dloss, class_weight, ignore_index, loss_weight)
+
+
+def ce_loss_up_fwd(src, target, loss_weight=1.0, ignore_index=255, class_weight=None, reduction='mean',
+                   avg_non_ignore=False):
+    """CrossEntropyLoss on bilinear(src -> target's H x W = 2 Hs x 2 Ws) without materialising the resized logits.
+    src [N,Hs,Ws,2] f32 -> (out[4], work)."""
+    return _ce_loss_fwd('ce_loss_up', True, src, target, class_weight, ignore_index, reduction, avg_non_ignore, loss_weight)
+
+
+def ce_loss_up_bwd(src, target, work, out, dloss, loss_weight=1.0, ignore_index=255, class_weight=None):
+    """-> dsrc [N,Hs,Ws,2]: the adjoint of the exact 2x resize applied to the loss gradient (never materialised)."""
+    return _ce_loss_bwd('ce_loss_up_bwd', True, src, target, work, out, dloss, class_weight, ignore_index, loss_weight)
+
+
+def _dice_class(ignore_class):
+    """DiceLoss.ignore_index is a class CHANNEL; None or a value outside the classes drops nothing"""
+    return -1 if ignore_class is None or not -(1 << 31) <= int(ignore_class) < (1 << 31) else int(ignore_class)
+
+
+def _dice_loss_fwd(who, up, logits, target, use_sigmoid, naive_dice, ignore_class, acc_ignore_index, reduction, eps,
+                   loss_weight):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, up, reduction)
+    if not eps >= 0:
+        raise LednError(f'{who}: eps={eps!r} must be >= 0')
+    work, out = _seg_loss_bufs(lib, N, logits)
+    _check(lib, logits, target, work, out)
+    cfg = (int(bool(use_sigmoid)), int(bool(naive_dice)), _dice_class(ignore_class), int(acc_ignore_index),
+           _REDUCTIONS[reduction], float(eps), float(loss_weight))
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{logits.shape[-1]}', _nb(logits, target), 20 * P * logits.shape[-1],
+                                           'sl_up_fwd_kernel' if up else 'sl_fwd_kernel')
+    if up:
+        _run(lib, 'ledn_dice_loss_up_fwd', logits, _p(logits), *shape, _p(target), *cfg, _p(work), _p(out), work=timing)
+    else:
+        _run(lib, 'ledn_dice_loss_fwd', logits, _p(logits), _p(target), *shape, *cfg, _p(work), _p(out), work=timing)
+    return out, work
+
+
+def _dice_loss_bwd(who, up, logits, target, work, out, dloss, use_sigmoid, naive_dice, ignore_class, reduction, eps,
+                   loss_weight):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, up, reduction)
+    dl = torch.empty_like(logits)
+    dloss = dloss.reshape(1).to(torch.float32).contiguous()
+    _check(lib, logits, target, work, out, dloss, dl)
+    cfg = (int(bool(use_sigmoid)), int(bool(naive_dice)), _dice_class(ignore_class), _REDUCTIONS[reduction], float(eps),
+           float(loss_weight))
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{logits.shape[-1]}', _nb(logits, target, dl), 30 * P * logits.shape[-1],
+                                           'sl_up_bwd_kernel' if up else 'sl_bwd_kernel')
+    if up:
+        _run(lib, 'ledn_dice_loss_up_bwd', logits, _p(logits), *shape, _p(target), *cfg, _p(work), _p(out), _p(dloss), _p(dl),
+             work=timing)
+    else:
+        _run(lib, 'ledn_dice_loss_bwd', logits, _p(logits), _p(target), *shape, *cfg, _p(work), _p(out), _p(dloss), _p(dl),
+             work=timing)
+    return dl
+
+
+def dice_loss_fwd(logits, target, loss_weight=1.0, use_sigmoid=True, naive_dice=False, ignore_class=255, eps=1e-3,
+                  reduction='mean', acc_ignore_index=255):
+    """DiceLoss: logits [N,H,W,C] f32, target [N,H,W] int64 -> (out[4] = loss, acc, 0, 0 ; work, whose first 4 N floats
+    are the per-image a, b, c, loss_n).  ignore_class: the dropped class channel (DiceLoss.ignore_index);
+    acc_ignore_index: the label left out of the accuracy."""
+    return _dice_loss_fwd('dice_loss', False, logits, target, use_sigmoid, naive_dice, ignore_class, acc_ignore_index,
+                          reduction, eps, loss_weight)
+
+
+def dice_loss_bwd(logits, target, work, out, dloss, loss_weight=1.0, use_sigmoid=True, naive_dice=False, ignore_class=255,
+                  eps=1e-3, reduction='mean'):
+    return _dice_loss_bwd('dice_loss_bwd', False, logits, target, work, out, dloss, use_sigmoid, naive_dice, ignore_class,
+                          reduction, eps, loss_weight)
+
+
+def dice_loss_up_fwd(src, target, loss_weight=1.0, use_sigmoid=True, naive_dice=False, ignore_class=255, eps=1e-3,
+                     reduction='mean', acc_ignore_index=255):
+    """DiceLoss on bilinear(src -> target's H x W = 2 Hs x 2 Ws) without materialising the resized logits."""
+    return _dice_loss_fwd('dice_loss_up', True, src, target, use_sigmoid, naive_dice, ignore_class, acc_ignore_index,
+                          reduction, eps, loss_weight)
+
+
+def dice_loss_up_bwd(src, target, work, out, dloss, loss_weight=1.0, use_sigmoid=True, naive_dice=False, ignore_class=255,
+                     eps=1e-3, reduction='mean'):
+    return _dice_loss_bwd('dice_loss_up_bwd', True, src, target, work, out, dloss, use_sigmoid, naive_dice, ignore_class,
+                          reduction, eps, loss_weight)
+
+
 def mfaf_ctx_fwd(pooled, seqs, training, stats1=None, momentum=0.1, tails=None, sync=None, world=1):
     """The four pooled-context MLPs of Muti_AFF in one launch sequence (ledn_mfaf_ctx_fwd).
     pooled: 4 f32 [N,S,S,C] maps; seqs: 4 x (conv1, bn1, conv2) modules.  -> (z2 list [N,S,S,C] f32, saved dict)

@@ -1370,6 +1370,44 @@ class OhemUp2Fn(Function):
         return d0, d1, None, None, None, None, None
 
 
+class SegLossFn(Function):
+    """CrossEntropyLoss / DiceLoss through csrc/seg_loss.hip: on NHWC logits (up = False) or on resize(src -> label
+    size) with the exact 2x resize folded into the kernels (up = True).  -> (loss, out[4])"""
+
+    @staticmethod
+    def forward(ctx, x, target, family, up, fwd_kw, bwd_kw):
+        fwd = getattr(T, f'{family}_loss_up_fwd' if up else f'{family}_loss_fwd')
+        out, work = fwd(x, target, **fwd_kw)
+        ctx.save_for_backward(x, target, work, out)
+        ctx.cfg = (family, up, bwd_kw)
+        ctx.mark_non_differentiable(out)
+        ctx.set_materialize_grads(False)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, dloss, _dout):
+        if dloss is None:
+            return None, None, None, None, None, None
+        x, target, work, out = ctx.saved_tensors
+        family, up, bwd_kw = ctx.cfg
+        bwd = getattr(T, f'{family}_loss_up_bwd' if up else f'{family}_loss_bwd')
+        return bwd(x, target, work, out, dloss, **bwd_kw), None, None, None, None, None
+
+
+def seg_loss_apply(crit, x, target, up, ignore_index):
+    """CrossEntropyLoss / DiceLoss `crit` on channels-last f32 `x` (up: x is the half-size source) -> (loss, out[4])"""
+    family, fwd_kw, bwd_kw = crit.kernel_args(x, ignore_index)
+    if up and target.data_ptr() % 16:
+        target = target.clone()          # (a view at an odd offset: the kernels read two labels per 16-byte load)
+    return SegLossFn.apply(x, target, family, up, fwd_kw, bwd_kw)
+
+
+def seg_loss(crit, score, target, ignore_index):
+    """CrossEntropyLoss.forward / DiceLoss.forward on NCHW(-view) logits."""
+    from .lednet import to_nhwc
+    return seg_loss_apply(crit, to_nhwc(score, torch.float32), target.contiguous(), False, ignore_index)[0]
+
+
 FUSE_LOSS_RESIZE = _knob_int('LEDN_FUSE_LOSS_RESIZE', 1)
 FUSE_LOSS_PAIR = _knob_int('LEDN_FUSE_LOSS_PAIR', 1)     # both losses in one launch set (ohem_fused.hip)
 
@@ -1388,9 +1426,27 @@ def led_head_loss_by_feat(h, seg_logits, batch_data_samples):
     hw = label.shape[2:]
     y = label.squeeze(1).contiguous()
     c0, c1 = h.loss_decode[0], h.loss_decode[1]
-    w0, w1 = c0.class_weight_on(xc), c1.class_weight_on(xc)      # None (the default) or the [C] device vector
     H, W = hw
-    if FUSE_LOSS_RESIZE and H % 2 == 0 and W % 2 == 0 and xc.shape[-1] == 2:
+    fold = bool(FUSE_LOSS_RESIZE and H % 2 == 0 and W % 2 == 0 and xc.shape[-1] == 2)
+    from .losses import OhemCrossEntropy
+    if not (isinstance(c0, OhemCrossEntropy) and isinstance(c1, OhemCrossEntropy)):
+        # CrossEntropyLoss / DiceLoss somewhere: each entry runs on its own (csrc/seg_loss.hip for the new losses, the
+        # single-loss OHEM kernels for an OhemCrossEntropy next to one of them)
+        losses, outs = [], []
+        for crit, logit in ((c0, xc), (c1, xs)):
+            x = fuse_loss_half(logit, h1, h2, hw) if fold else fuse_loss(logit, h1, h2, hw)
+            if isinstance(crit, OhemCrossEntropy):
+                l, out = (OhemUpFn if fold else OhemFn).apply(x, y, crit.thresh, crit.min_kept, crit.loss_weight,
+                                                              crit.ignore_label, crit.class_weight_on(x))
+            else:
+                # the head's ignore_index, as BaseDecodeHead.loss_by_feat passes it (the reference's LEDHead passes
+                # none: its CrossEntropyLoss then runs with -100 and raises on the first padded pixel)
+                l, out = seg_loss_apply(crit, x, y, fold, h.ignore_index)
+            losses.append(l)
+            outs.append(out)
+        return {'loss_context': losses[0], 'loss_spatial': losses[1], 'acc_seg': outs[0][1:2]}
+    w0, w1 = c0.class_weight_on(xc), c1.class_weight_on(xc)      # None (the default) or the [C] device vector
+    if fold:
         # the last (exact 2x) resize of each fused output runs inside the loss kernels: the full-resolution logits
         # and their gradient are never written
         ctx2, spa2 = fuse_loss_half(xc, h1, h2, hw), fuse_loss_half(xs, h1, h2, hw)
