@@ -135,7 +135,8 @@ int ledn_stats_defer_begin(void);
 int ledn_stats_defer_end(float** part, int* rows);
 /* Pure query, no launch: 1 if ledn_conv2d would run this descriptor on conv_mfma_kernel, 2 if on
  * conv1x1_mfma_kernel, 3 if on conv3x3_reg_kernel, 4 if on conv3x3_narrowin_mfma_kernel, 5 if on conv_f32_mfma_kernel
- * (f32 activations on v_mfma_f32_32x32x2_f32, csrc/conv_f32.hip) (all matrix cores), 0 if on
+ * (f32 activations on v_mfma_f32_32x32x2_f32, csrc/conv_f32.hip), 6 if on head_fwd_kernel, 7 / 8 if on head_mc_fwd_kernel /
+ * head_mc_dgrad_kernel (the heads with 3 .. 32 classes, csrc/head_mc.hip) (all matrix cores), 0 if on
  * conv_direct_kernel / conv_narrowin_kernel (VALU).  bench.py names the kernel in its
  * roofline with it. */
 int ledn_conv2d_uses_mfma(const ledn_conv_desc* d);
@@ -217,7 +218,7 @@ typedef struct {
     const float* in_slope; /* [Cin] when in_act == PRELU */
 } ledn_wgrad_desc;
 int ledn_conv2d_wgrad(const ledn_wgrad_desc* d, void* stream);
-int ledn_conv2d_wgrad_uses_mfma(const ledn_wgrad_desc* d);   /* same query for the weight gradient: 1 conv_wgrad_mfma_kernel, 2 conv3x3_wgrad_narrow_kernel, 3 conv1x1_wgrad_reg_kernel (csrc/conv3x3.hip), 4 conv_wgrad_f32_mfma_kernel (f32 activations, csrc/conv_f32.hip), 0 the VALU kernels */
+int ledn_conv2d_wgrad_uses_mfma(const ledn_wgrad_desc* d);   /* same query for the weight gradient: 1 conv_wgrad_mfma_kernel, 2 conv3x3_wgrad_narrow_kernel, 3 conv1x1_wgrad_reg_kernel (csrc/conv3x3.hip), 4 conv_wgrad_f32_mfma_kernel (f32 activations, csrc/conv_f32.hip), 5 head_mc_wgrad_kernel (csrc/head_mc.hip), 0 the VALU kernels */
 /* Deferred reduction of the weight gradient.  ledn_conv2d_wgrad runs the MFMA kernel (per-workgroup partial tiles into the
  * stream's workspace) and then a small summing launch -- ~55 of them per training step, each on the critical path of the
  * stream although nothing reads dW before the optimizer.  ledn_conv2d_wgrad_partial instead writes the partial tiles into a
@@ -614,7 +615,24 @@ int ledn_bn_act_bwd_fused_check(int C, void* stream);
  * w is rounded to bf16 for the matrix instruction (as in the MFMA data-gradient kernels it replaces); dy stays f32
  * (the layer-wise form rounds it to bf16 once).
  * Supported (ledn_head_bwd_supported != 0): Co = 2, C = 32, bf16 x and head_dz, >= 16384 pixels, a bound workspace;
- * otherwise LEDN_EINVAL and the caller uses the layer-wise entries. */
+ * otherwise LEDN_EINVAL and the caller uses the layer-wise entries.
+ *
+ * More than two classes (csrc/head_mc.hip): no entry point of their own.  ledn_conv2d and ledn_conv2d_wgrad run the heads'
+ * norm -> act -> conv3x3 (pad 1, stride 1, dilation 1, one group, 32 -> Co) on head_mc_fwd_kernel / head_mc_dgrad_kernel /
+ * head_mc_wgrad_kernel (ledn_conv2d_uses_mfma 7 / 8, ledn_conv2d_wgrad_uses_mfma 5) when ALL of: 3 <= Co <= 32; bf16
+ * activations (x; dz for the gradients); >= 1024 pixels and < 2^31 / 32 of them; natural OIHW weight strides;
+ * LEDN_OPT_STREAM_FAST bit 6; and
+ *   forward:  in_scale and in_shift given (the norm in front), in_act none / ReLU / PReLU, y bf16 or f32, out_scale /
+ *             out_shift optional, act_out none / ReLU, no xadd / residual / statistics (ledn_channel_stats forms them);
+ *   data gradient (transposed = 1): Cin = Co, Cout = 32, bf16 dy, no prologue / epilogue / residual and NO w_bf16 (a caller
+ *             that passes ledn_pack_conv_weights' pack gets the general matrix-core kernels);
+ *   weight gradient: in_scale and in_shift given, bf16 dz; needs the bound workspace (Co * 288 floats per workgroup; the
+ *             grid shrinks to what fits, LEDN_EINVAL when not one row does -- no silent fall-back, the query stays true);
+ *             dw / db are accumulated; fixed summation order in deterministic mode.
+ * Forward and weight gradient read the f32 filter and round it themselves: a w_bf16 pack passed along is ignored.
+ * The BatchNorm backward of these heads is the layer-wise pair ledn_bn_act_bwd_reduce / _apply on the dy the data gradient
+ * wrote.  Everything else (Co = 2, Co > 32, f32 activations) keeps the kernels it had.  LEDN_HEAD_MC=0 (with
+ * LEDN_EXPERIMENTAL=1, read once) switches the three kernels off. */
 typedef struct {
     ledn_bnbwd_desc bn;
     const void* head_dz;    /* [N][H][W][Co] bf16 (dtype_dz): gradient of the head's logits */

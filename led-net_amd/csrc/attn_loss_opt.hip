@@ -610,7 +610,9 @@ __global__ void __launch_bounds__(256) ohem_hist_kernel(float* work, long P, int
         if (s_hist[i]) atomicAdd(&h[i], s_hist[i]);
 }
 
-__global__ void __launch_bounds__(256) ohem_reduce_kernel(float* work, long P) {
+// part (deterministic mode): one (sum, count) row per workgroup instead of the two atomics; ohem_final_kernel adds the rows
+// in row order
+__global__ void __launch_bounds__(256) ohem_reduce_kernel(float* work, long P, float* part) {
     __shared__ float s_sum[4];
     __shared__ unsigned s_cnt[4];
     const OhemWork w = ohem_work(work, P);
@@ -632,15 +634,31 @@ __global__ void __launch_bounds__(256) ohem_reduce_kernel(float* work, long P) {
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(reinterpret_cast<float*>(&w.state[6]), s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
-        atomicAdd(&w.state[5], s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
+        const float bs = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+        const unsigned bc = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (part) {
+            part[2 * blockIdx.x] = bs;
+            part[2 * blockIdx.x + 1] = __uint_as_float(bc);
+        } else {
+            atomicAdd(reinterpret_cast<float*>(&w.state[6]), bs);
+            atomicAdd(&w.state[5], bc);
+        }
     }
 }
 
-__global__ void ohem_final_kernel(float* work, long P, float loss_weight, float* out) {
+__global__ void ohem_final_kernel(float* work, long P, float loss_weight, float* out, const float* part, int nparts) {
     const OhemWork w = ohem_work(work, P);
-    const unsigned nv = w.state[0], nsel = w.state[5];
-    const float sum = __uint_as_float(w.state[6]);
+    const unsigned nv = w.state[0];
+    unsigned nsel = w.state[5];
+    float sum = __uint_as_float(w.state[6]);
+    if (part) {
+        sum = 0.f;
+        nsel = 0u;
+        for (int b = 0; b < nparts; ++b) {
+            sum += part[2 * b];
+            nsel += __float_as_uint(part[2 * b + 1]);
+        }
+    }
     out[0] = nv == 0u ? 0.f : loss_weight * (sum / (float)nsel);   // 0/0 -> NaN like the reference
     const float eps = 1.1920929e-07f;
     out[1] = ((float)w.state[1] + eps) * (100.0f / ((float)nv + eps));
@@ -668,8 +686,13 @@ int ohem_ce_fwd_impl(const float* logits, const long long* target, long long P, 
     LEDN_LAUNCH(ohem_scan_kernel, dim3(1), dim3(256), 0, s, work, (long)P, 1, min_kept, thres);
     LEDN_LAUNCH(ohem_hist_kernel, grid, dim3(256), 0, s, work, (long)P, 2);
     LEDN_LAUNCH(ohem_scan_kernel, dim3(1), dim3(256), 0, s, work, (long)P, 2, min_kept, thres);
-    LEDN_LAUNCH(ohem_reduce_kernel, grid, dim3(256), 0, s, work, (long)P);
-    LEDN_LAUNCH(ohem_final_kernel, dim3(1), dim3(1), 0, s, work, (long)P, loss_weight, out);
+    // deterministic mode: no float atomics.  The rows overlay the workspace base like every two-stage reduction: nothing is
+    // pending there -- deferred BatchNorm rows live only between a producer and the bn_finalize that follows it at once
+    // (include/ledn.h, ledn_conv2d_deferred_stats), and no loss sits between such a pair
+    float* part = det() ? ws_take(2L * grid.x) : nullptr;
+    if (det() && !part) return LEDN_EINVAL;
+    LEDN_LAUNCH(ohem_reduce_kernel, grid, dim3(256), 0, s, work, (long)P, part);
+    LEDN_LAUNCH(ohem_final_kernel, dim3(1), dim3(1), 0, s, work, (long)P, loss_weight, out, (const float*)part, (int)grid.x);
     return check_launch();
 }
 
@@ -801,8 +824,13 @@ int ohem_ce_up_fwd_impl(const float* src, int N, int Hs, int Ws, int H, int W, c
     LEDN_LAUNCH(ohem_scan_kernel, dim3(1), dim3(256), 0, s, work, (long)P, 1, min_kept, thres);
     LEDN_LAUNCH(ohem_hist_kernel, grid, dim3(256), 0, s, work, (long)P, 2);
     LEDN_LAUNCH(ohem_scan_kernel, dim3(1), dim3(256), 0, s, work, (long)P, 2, min_kept, thres);
-    LEDN_LAUNCH(ohem_reduce_kernel, grid, dim3(256), 0, s, work, (long)P);
-    LEDN_LAUNCH(ohem_final_kernel, dim3(1), dim3(1), 0, s, work, (long)P, loss_weight, out);
+    // deterministic mode: no float atomics.  The rows overlay the workspace base like every two-stage reduction: nothing is
+    // pending there -- deferred BatchNorm rows live only between a producer and the bn_finalize that follows it at once
+    // (include/ledn.h, ledn_conv2d_deferred_stats), and no loss sits between such a pair
+    float* part = det() ? ws_take(2L * grid.x) : nullptr;
+    if (det() && !part) return LEDN_EINVAL;
+    LEDN_LAUNCH(ohem_reduce_kernel, grid, dim3(256), 0, s, work, (long)P, part);
+    LEDN_LAUNCH(ohem_final_kernel, dim3(1), dim3(1), 0, s, work, (long)P, loss_weight, out, (const float*)part, (int)grid.x);
     return check_launch();
 }
 

@@ -219,6 +219,7 @@ int ledn_conv2d(const ledn_conv_desc* d, void* stream) {
     const int rc = conv_validate(*d);
     if (rc != LEDN_OK) return rc;
     if (head_fwd_supported(*d)) return head_fwd(*d, S(stream));      // the two-class heads (head_bwd.hip)
+    if (head_mc_conv_kind(*d)) return head_mc_conv(*d, S(stream));   // the heads with 3 .. 32 classes (head_mc.hip)
     if (conv_mfma_supported(*d)) {
         if (conv1x1_reg_supported(*d)) return conv1x1_reg(*d, S(stream));
         if (conv3x3_reg_supported(*d)) return conv3x3_reg(*d, S(stream));
@@ -274,12 +275,14 @@ int ledn_bn_finalize_rows(const float* part, int rows, double count, const float
 
 int ledn_conv2d_uses_mfma(const ledn_conv_desc* d) {
     if (d && conv_validate(*d) == LEDN_OK && head_fwd_supported(*d)) return 6;
+    if (d && conv_validate(*d) == LEDN_OK && head_mc_conv_kind(*d)) return 6 + head_mc_conv_kind(*d);   // 7 forward, 8 data gradient
     if (d && !conv_mfma_supported(*d) && conv3x3_narrowin_mfma_supported(*d)) return 4;
     if (d && !conv_mfma_supported(*d) && conv_validate(*d) == LEDN_OK && conv_f32_mfma_supported(*d)) return 5;
     if (!d || !conv_mfma_supported(*d)) return 0;
     return conv1x1_reg_supported(*d) ? 2 : (conv3x3_reg_supported(*d) ? 3 : 1);
 }
 int ledn_conv2d_wgrad_uses_mfma(const ledn_wgrad_desc* d) {
+    if (d && wgrad_validate(*d) == LEDN_OK && !conv_wgrad_cout2_supported(*d) && head_mc_wgrad_supported(*d)) return 5;
     if (d && !conv_wgrad_cout2_supported(*d) && conv_wgrad_narrow_reg_supported(*d)) return 2;
     if (d && !conv_wgrad_cout2_supported(*d) && conv1x1_wgrad_reg_applies(*d)) return 3;
     if (d && !conv_wgrad_cout2_supported(*d) && wgrad_mfma_supported(*d)) return 1;
@@ -309,6 +312,12 @@ int ledn_conv2d_wgrad(const ledn_wgrad_desc* d, void* stream) {
     const int rc = wgrad_validate(*d);
     if (rc != LEDN_OK) return rc;
     if (conv_wgrad_cout2_supported(*d)) return conv_wgrad_cout2(*d, S(stream));   // two-class heads
+    if (head_mc_wgrad_supported(*d)) {                                             // the heads with 3 .. 32 classes (head_mc.hip)
+        const int r2 = head_mc_wgrad(*d, S(stream));
+        if (r2 != LEDN_OK || !d->db) return r2;
+        return channel_stats_impl(d->dz, nullptr, (long long)d->N * d->Ho * d->Wo, d->Cout, d->dtype_dz, d->db,
+                                  nullptr, S(stream));
+    }
     if (conv_wgrad_narrow_reg_supported(*d)) {                                     // ... their 3x3 layers
         const int r2 = conv_wgrad_narrow_reg(*d, S(stream));
         if (r2 != LEDN_OK || !d->db) return r2;
@@ -329,8 +338,8 @@ int ledn_conv2d_wgrad(const ledn_wgrad_desc* d, void* stream) {
 }
 
 long long ledn_conv2d_wgrad_partial_floats(const ledn_wgrad_desc* d) {
-    if (!d || wgrad_validate(*d) != LEDN_OK || conv_wgrad_cout2_supported(*d) || conv_wgrad_narrow_reg_supported(*d) ||
-        !wgrad_mfma_supported(*d))
+    if (!d || wgrad_validate(*d) != LEDN_OK || conv_wgrad_cout2_supported(*d) || head_mc_wgrad_supported(*d) ||
+        conv_wgrad_narrow_reg_supported(*d) || !wgrad_mfma_supported(*d))
         return 0;
     ledn_wgrad_finish_entry e;
     if (conv_wgrad_mfma_partial(*d, nullptr, 0, &e, true, nullptr) != LEDN_OK || e.nbx <= 4) return 0;

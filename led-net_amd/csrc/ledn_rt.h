@@ -421,6 +421,11 @@ int head_bwd_reduce(const ledn_headbwd_desc& d, hipStream_t s);
 int head_bwd_apply(const ledn_headbwd_desc& d, hipStream_t s);
 bool head_fwd_supported(const ledn_conv_desc& d);
 int head_fwd(const ledn_conv_desc& d, hipStream_t s);
+// head_mc.hip: the heads with 3 .. 32 classes (kind 1 forward, 2 data gradient, 0 not handled)
+int head_mc_conv_kind(const ledn_conv_desc& d);
+int head_mc_conv(const ledn_conv_desc& d, hipStream_t s);
+bool head_mc_wgrad_supported(const ledn_wgrad_desc& d);
+int head_mc_wgrad(const ledn_wgrad_desc& d, hipStream_t s);
 int channel_stats_fast(const void* x, const void* xadd, long long P, int C, int dtype, float* sum, float* sqsum,
                        hipStream_t s);
 // seg_loss.hip: the loss of a ledn_ce_loss_* / ledn_dice_loss_* call and its settings

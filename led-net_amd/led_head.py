@@ -5,6 +5,12 @@ Mirrors mmseg/models/decode_heads/led_head.py:15-146 and the LED-specific
 same constructor arguments, attribute names, state_dict keys
 (``head.0.bn``, ``head.0.conv``, ``head.1``, ``conv_seg``, ``aux_cls_seg`` ...),
 methods ``forward / loss / predict / loss_by_feat / predict_by_feat``.
+
+One divergence: the reference builds ``head_x1`` / ``head_x2`` as ``_make_base_head(32, 2)`` (led_head.py:47-48, a
+literal 2), so it cannot run with any other ``num_classes`` -- its first fused add then meets 2 against num_classes
+channels.  Here the two heads are ``num_classes`` (``out_channels``) wide: identical for the shipped two-class config
+(same keys, shapes and initialisation), and Cityscapes' 19 or CamVid's 11 classes build, train and predict.  Their 3x3
+convolutions run on csrc/head_mc.hip for 3 .. 32 classes.
 """
 import math
 
@@ -35,9 +41,10 @@ class LEDHead(Block):
         self.sync_bn = bool(norm_cfg and norm_cfg.get('type') == 'SyncBN')
         self.head = self._make_base_head(in_channels, channels)
         self.aux_head = self._make_base_head(in_channels // 2, channels)
-        # led_head.py:47-48 hard-codes (32, 2); identical for the shipped config
-        self.head_x1 = self._make_base_head(32, 2)
-        self.head_x2 = self._make_base_head(32, 2)
+        # led_head.py:47-48 hard-codes (32, 2); here the class count (see the module docstring): identical for the shipped
+        # config.  32 = the backbone's `channels` in every config.
+        self.head_x1 = self._make_base_head(32, self.out_channels)
+        self.head_x2 = self._make_base_head(32, self.out_channels)
         self.conv_seg = nn.Conv2d(channels, self.out_channels, 1)
         self.aux_cls_seg = nn.Conv2d(channels, self.out_channels, 1)
         from .losses import build_loss

@@ -272,13 +272,14 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, groups=1, xadd=None, in_scale=None, 
     _run_stats(lib, 'ledn_conv2d', x, stats, defer_stats, d, work=_TIMING is not None and (
         f'conv{KH}x{KW}{"T" if transposed else ""} {Cin}->{Cout} g{groups} s{stride} {N}x{H}x{W} {str(x.dtype)[6:]}',
         _nb(x, xadd, y, res, w), 2 * N * Ho * Wo * Cout * (Cin // groups) * KH * KW,
-        ('conv_direct_kernel', 'conv_mfma_kernel', 'conv1x1_mfma_kernel', 'conv3x3_reg_kernel', 'conv3x3_narrowin_mfma_kernel', 'conv_f32_mfma_kernel', 'head_fwd_kernel')[lib.cdll.ledn_conv2d_uses_mfma(d)]))
+        ('conv_direct_kernel', 'conv_mfma_kernel', 'conv1x1_mfma_kernel', 'conv3x3_reg_kernel', 'conv3x3_narrowin_mfma_kernel', 'conv_f32_mfma_kernel', 'head_fwd_kernel', 'head_mc_fwd_kernel', 'head_mc_dgrad_kernel')[lib.cdll.ledn_conv2d_uses_mfma(d)]))
     return y
 
 
 def conv2d_kernel_id(x, w, **kw):
     """which kernel ledn_conv2d runs these arguments on (no launch): 0 conv_direct_kernel (VALU), 1 conv_mfma_kernel,
-    2 conv1x1_mfma_kernel, 3 conv3x3_reg_kernel, 4 conv3x3_narrowin_mfma_kernel, 5 conv_f32_mfma_kernel, 6 head_fwd_kernel"""
+    2 conv1x1_mfma_kernel, 3 conv3x3_reg_kernel, 4 conv3x3_narrowin_mfma_kernel, 5 conv_f32_mfma_kernel, 6 head_fwd_kernel,
+    7 head_mc_fwd_kernel, 8 head_mc_dgrad_kernel (the heads with 3 .. 32 classes, csrc/head_mc.hip)"""
     return conv2d(x, w, _query=True, **kw)
 
 
@@ -466,7 +467,7 @@ def conv2d_wgrad(x, dz, w_shape, *, stride=1, pad=0, dil=1, groups=1, xadd=None,
     """Returns (dw [OIHW f32], db or None) of conv2d(pre(x), w).  dw_out / db_out: contiguous f32
     tensors the gradients are ACCUMULATED into (the trainer's flat gradient buffer) instead of
     fresh zeroed ones.  _query: no launch -> ledn_conv2d_wgrad_uses_mfma (0 VALU kernels, 1 conv_wgrad_mfma_kernel,
-    2 conv3x3_wgrad_narrow_kernel, 3 conv1x1_wgrad_reg_kernel)."""
+    2 conv3x3_wgrad_narrow_kernel, 3 conv1x1_wgrad_reg_kernel, 4 conv_wgrad_f32_mfma_kernel, 5 head_mc_wgrad_kernel)."""
     lib = _lib.get_lib()
     N, H, W, Cin = x.shape
     cof, cigf, KH, KW = w_shape
@@ -513,7 +514,7 @@ def conv2d_wgrad(x, dz, w_shape, *, stride=1, pad=0, dil=1, groups=1, xadd=None,
             return dw, db
     _run(lib, 'ledn_conv2d_wgrad', x, d,
          work=_TIMING is not None and (f'wgrad{KH}x{KW} {Cin}->{Cout} g{groups} s{stride} {N}x{H}x{W}', _nb(x, xadd, dz, dw), flops,
-                                       ('conv_wgrad_direct', 'conv_wgrad_mfma_kernel', 'conv3x3_wgrad_narrow_kernel', 'conv1x1_wgrad_reg_kernel', 'conv_wgrad_f32_mfma_kernel')[lib.cdll.ledn_conv2d_wgrad_uses_mfma(d)]))
+                                       ('conv_wgrad_direct', 'conv_wgrad_mfma_kernel', 'conv3x3_wgrad_narrow_kernel', 'conv1x1_wgrad_reg_kernel', 'conv_wgrad_f32_mfma_kernel', 'head_mc_wgrad_kernel')[lib.cdll.ledn_conv2d_wgrad_uses_mfma(d)]))
     return dw, db
 
 

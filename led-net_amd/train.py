@@ -363,12 +363,26 @@ def _conv_wgrad(x, dz, w_shape, sw, sb, **kw):
     return ops.conv2d_wgrad(x, dz, w_shape, dw_out=sw, db_out=sb, **kw)
 
 
-def _conv_dgrad(dz, x, w, stride, pad, groups, acc=None):
+_HEAD_MC_DGRAD = {}
+
+
+def _conv_dgrad(dz, x, w, stride, pad, groups, acc=None, head=False):
     """data gradient of conv2d(x, w): MFMA path when the flipped pack applies (see ConvFn.backward).
-    acc: gradient fan-in of x (_Acc): the partial gradient of x's other consumers enters as the epilogue's residual."""
+    acc: gradient fan-in of x (_Acc): the partial gradient of x's other consumers enters as the epilogue's residual.
+    head: a norm -> act -> conv module without output statistics (LEDHead's base heads; the LEDN_FUSE_BN_CONV=2 backbone
+    layers carry statistics and keep their packed kernels): with 3 .. 32 classes its gradient runs on head_mc_dgrad_kernel, which
+    reads the f32 filter itself (no pack: a pack asks for the general kernels)."""
     wp = None
     cin_f = w.shape[1] * groups     # dgrad kernel: "Cin" = Cout_f (16-multiple), "Cout" = Cin_f
-    if (dz.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and w.shape[0] % 16 == 0
+    head_mc = False
+    if head and 3 <= w.shape[0] <= 32 and dz.dtype == torch.bfloat16 and x.dtype == torch.bfloat16:
+        key = (tuple(dz.shape), tuple(w.shape), stride, pad, groups, x.shape[1], x.shape[2])
+        head_mc = _HEAD_MC_DGRAD.get(key)
+        if head_mc is None:         # (asked once per shape: the query builds a descriptor with an output tensor)
+            head_mc = _HEAD_MC_DGRAD[key] = ops.conv2d_kernel_id(
+                dz, w, stride=stride, pad=pad, groups=groups, transposed=True, out_hw=(x.shape[1], x.shape[2]),
+                out_dtype=x.dtype) == 8
+    if (not head_mc and dz.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and w.shape[0] % 16 == 0
             and (cin_f % 16 == 0 or cin_f <= 8) and ops.mfma_weight_ok(w, groups)):
         wp = get_pack(w, 1, groups)
     # (addend: the MFMA kernel's epilogue residual; f32 activations: the direct kernel's.  The narrow bf16 direct
@@ -413,6 +427,7 @@ class BNActConvFn(Function):
                        defer_stats=st is not None and _Env.sync_bn is None)   # a BNActFn on stats_out follows
         ctx.save_for_backward(x, w, scale, shift, mean, invstd, slope)
         ctx.cfg = (act, count, stride, pad, groups, b is not None)
+        ctx.is_head = stats_out is None      # conv_module's norm-first form: LEDHead's base heads
         ctx.sinks = (_Sinks.get(gamma), _Sinks.get(beta), _Sinks.get(slope), _Sinks.get(w), _Sinks.get(b))
         ctx.acc = acc
         return z
@@ -433,7 +448,7 @@ class BNActConvFn(Function):
         else:
             dw, db = _conv_wgrad(x, dz, tuple(w.shape), sw, sbias, stride=stride, pad=pad, groups=groups, in_scale=scale,
                                  in_shift=shift, in_act=act, in_slope=slope, bias=has_b)
-        dy = _conv_dgrad(dz, x, w, stride, pad, groups) if head is None else None
+        dy = _conv_dgrad(dz, x, w, stride, pad, groups, head=ctx.is_head) if head is None else None
         prev = _take(ctx.acc, x)
         dx, _, dgamma, dbeta, dslope = T.bn_act_bwd(x, dy, scale=scale, shift=shift, mean=mean, invstd=invstd,
                                                      act=act, slope=slope, count=count, sync=_Env.sync_bn,

@@ -113,20 +113,21 @@ def main():
     gdev = torch.Generator(device=dev)
     side = torch.cuda.Stream(device=dev)
     H, W = args.height, args.width
+    ncls = int(model.decode_head.num_classes)      # synthetic labels cover every class of the head
 
     def make_batch(it):
         gdev.manual_seed(304 + 7919 * rank + 1000003 * it)
         if pipe is not None:                # "decoded" H x 2W images + label maps -> augmented crops, one launch
             np.random.seed((304 + 7919 * rank + 1000003 * it) % (2 ** 32))
             raw = torch.randint(0, 256, (bs, H, 2 * W, 3), dtype=torch.uint8, device=dev, generator=gdev)
-            seg = torch.randint(0, 2, (bs, H // 8, W // 4), dtype=torch.uint8, device=dev, generator=gdev)
+            seg = torch.randint(0, ncls, (bs, H // 8, W // 4), dtype=torch.uint8, device=dev, generator=gdev)
             seg = seg.repeat_interleave(8, 1).repeat_interleave(8, 2).contiguous()
             aug = pipe.batch([dict(img=raw[i], gt_seg_map=seg[i]) for i in range(bs)], out_hw=(H, W))
             # padded_samples carry img_shape / pad_shape / padding_size: the stem then writes pad_val in the
             # NORMALISED domain over the padded area, as SegDataPreProcessor.forward(training=True) + stack_batch do
             return aug['batch'], aug['padded_samples']
         img = torch.randint(0, 256, (bs, 3, H, W), dtype=torch.uint8, device=dev, generator=gdev)
-        lab = torch.randint(0, 2, (bs, 1, H, W), dtype=torch.int64, device=dev, generator=gdev)
+        lab = torch.randint(0, ncls, (bs, 1, H, W), dtype=torch.int64, device=dev, generator=gdev)
         lab[:, :, :16], lab[:, :, -16:], lab[..., :16], lab[..., -16:] = 255, 255, 255, 255
         return img, [L.SegDataSample(gt=lab[i]) for i in range(bs)]
 
@@ -140,7 +141,9 @@ def main():
 
     def save(it):
         L.save_checkpoint(model, osp.join(work_dir, f'iter_{it}.pth'), trainer=trainer,
-                          meta=dict(iter=it, dataset_meta=dict(classes=('background', 'foreground'), palette=None)))
+                          meta=dict(iter=it, dataset_meta=dict(
+                              classes=('background', 'foreground') if ncls == 2 else tuple(str(i) for i in range(ncls)),
+                              palette=None)))
 
     use_graph = not args.eager
     if use_graph and trainer.dist is not None and trainer.comm is None:
