@@ -1053,6 +1053,30 @@ typedef struct {
 int ledn_optim_step(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d,
                     void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Weight averaging (mmengine EMAHook: ExponentialMovingAverage / ExpMomentumEMA), folded into the optimizer launch.
+ *
+ * ledn_optim_step_ema: ledn_optim_step plus one averaged copy per tensor, avg_table_dev[i] (n_tensors device pointers,
+ *   parallel to table_dev; ledn_optim_entry is unchanged).  The thread that forms the new p also writes
+ *       avg <- avg + w * (p_new - avg)          0 < w < 1
+ *       avg <- p_new  (avg is not read)         w >= 1: the hook's first update, and every iteration before begin_iter
+ *   w: the argument, or *w_dev when w_dev != NULL (one device float: a captured graph replays with a new value; keeping
+ *   it in (0, 1] is then the caller's business).  p, g, m, v come out with the bits of ledn_optim_step on the same
+ *   inputs.  16-byte accesses for a tensor whose p, g, m, v AND avg are 16-byte aligned, 4-byte accesses otherwise.
+ *   LEDN_EINVAL: what ledn_optim_step rejects, a NULL avg_table_dev, w outside (0, 1] with w_dev == NULL.
+ * ledn_ema_update: the same update for tensors the optimizer launch does not touch (frozen parameters, BatchNorm
+ *   running statistics), over a device table of {avg, src, n}; one launch, no atomics, the same bits in either
+ *   determinism mode.  LEDN_EINVAL: NULL table, n_tensors / max_n <= 0, w outside (0, 1] with w_dev == NULL. */
+typedef struct {
+    float* avg;
+    const float* src;
+    long long n;
+} ledn_ema_entry;
+int ledn_optim_step_ema(const ledn_optim_entry* table_dev, float* const* avg_table_dev, int n_tensors, long long max_n,
+                        const ledn_optim_desc* d, float w, const float* w_dev, void* stream);
+int ledn_ema_update(const ledn_ema_entry* table_dev, int n_tensors, long long max_n, float w, const float* w_dev,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,10 @@ class OptimEntry(C.Structure):          # mirrors ledn_optim_entry
     _fields_ = [('p', fp), ('g', fp), ('m', fp), ('v', fp), ('n', i64), ('lr_mult', C.c_float), ('wd_mult', C.c_float)]
 
 
+class EmaEntry(C.Structure):            # mirrors ledn_ema_entry
+    _fields_ = [('avg', fp), ('src', fp), ('n', i64)]
+
+
 class OptimDesc(C.Structure):           # mirrors ledn_optim_desc
     _fields_ = [('kind', i32), ('has_v', i32), ('lr_a', C.c_float), ('lr_b', C.c_float), ('sched_dev', fp),
                 ('momentum', C.c_float), ('eps', C.c_float), ('beta1', C.c_double), ('beta2', C.c_double),
@@ -235,6 +239,8 @@ _PROTOS = {
     'ledn_sgd_step_clip': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, fp, i32, i32, C.c_float, C.c_float,
                             fp, vp], i32),
     'ledn_optim_step': ([vp, i32, i64, C.POINTER(OptimDesc), vp], i32),
+    'ledn_optim_step_ema': ([vp, vp, i32, i64, C.POINTER(OptimDesc), C.c_float, fp, vp], i32),
+    'ledn_ema_update': ([vp, i32, i64, C.c_float, fp, vp], i32),
     'ledn_abi_version': ([], i32),
     'ledn_set_workspace': ([vp, i64], i32),
     'ledn_bind_workspace': ([vp, vp, i64], i32),

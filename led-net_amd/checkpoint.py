@@ -47,6 +47,13 @@ def save_checkpoint(model, filename, meta=None, trainer=None):
     the reference stack pins it)."""
     sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     ckpt = {'meta': dict(meta or {}), 'state_dict': sd}
+    if trainer is not None and getattr(trainer, 'ema', None) is not None:
+        # mmengine EMAHook's swap: 'state_dict' holds the AVERAGED weights (what test.py / init_model evaluate),
+        # 'ema_state_dict' the averaged model's counter and, under 'module.', the training weights
+        ema = trainer.ema_state()
+        ckpt['state_dict'] = ema['state_dict']
+        ckpt['ema_state_dict'] = {'steps': torch.tensor(ema['steps'], dtype=torch.int64)}
+        ckpt['ema_state_dict'].update({'module.' + k: v for k, v in sd.items()})
     ckpt['meta'].setdefault('epoch', 0)
     if trainer is not None:
         ckpt['optimizer'] = trainer.optimizer_state_dict()
@@ -62,7 +69,23 @@ def save_checkpoint(model, filename, meta=None, trainer=None):
 
 def resume(trainer, ckpt):
     """restore the optimizer / schedule state of a checkpoint dict (as returned by load_checkpoint) into a
-    Trainer; weights-only checkpoints restart with zero momentum (and say so)."""
+    Trainer; weights-only checkpoints restart with zero momentum (and say so).  A checkpoint of an EMAHook run holds
+    the averaged weights in 'state_dict' and the training weights in 'ema_state_dict': the swap is undone here (the model
+    must be the one load_checkpoint filled from this dict)."""
+    ema_sd = ckpt.get('ema_state_dict')
+    if ema_sd is not None:
+        model = trainer.model
+        if getattr(trainer, 'ema', None) is not None:
+            trainer.load_ema_state(int(ema_sd.get('steps', 0)), _strip(ckpt['state_dict'], 'module.'))
+        train_sd = {k[len('module.'):]: v for k, v in ema_sd.items() if k.startswith('module.')}
+        model.load_state_dict(train_sd, strict=False)
+        for m in model.modules():
+            cache = getattr(m, '_cache', None)
+            if isinstance(cache, dict):
+                cache.clear()
+    elif getattr(trainer, 'ema', None) is not None:
+        warnings.warn('checkpoint has no ema_state_dict: the weight average starts from the loaded weights (steps = 0)')
+        trainer.load_ema_state(0, {})
     if 'optimizer' in ckpt:
         trainer.load_optimizer_state_dict(ckpt['optimizer'], ckpt.get('param_schedulers'), ckpt.get('meta', {}).get('iter'))
     else:

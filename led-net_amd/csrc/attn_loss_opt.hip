@@ -1227,10 +1227,121 @@ __global__ void __launch_bounds__(256) optim_kernel(const OptimArgs a) {
     }
 }
 
+// weight averaging folded into the launch (ledn_optim_step_ema): avg <- avg + w * (p_new - avg) by the thread that formed
+// p_new.  w >= 1 (the hook's first step, or an iteration before begin_iter) is a copy: p_new itself is stored and avg is
+// not read -- avg + 1 * (p - avg) is not p in f32, and an uninitialised or non-finite avg would come out NaN.
+__device__ __forceinline__ float ema_lerp(float w, float avg, float p) { return opt_fma(w, opt_add(p, -avg), avg); }
+
+// optim_kernel with the averaged column.  A kernel of its own and not a template switch on optim_kernel: routing the
+// shared body through a helper changed the code of the existing launch (flat instead of global accesses, other fused
+// products), and ledn_optim_step has to stay what it was.  Everything up to the store of p is optim_kernel's text.
+template <int KIND, int CLIP>
+__global__ void __launch_bounds__(256) optim_ema_kernel(const OptimArgs a, float* const* avgs, float w_arg, const float* w_dev) {
+    const ledn_optim_entry e = a.table[blockIdx.y];
+    float* const avg = avgs[blockIdx.y];
+    const bool vec = ((((uintptr_t)e.p | (uintptr_t)e.g | (uintptr_t)e.m | (uintptr_t)e.v | (uintptr_t)avg) & 15u) == 0) && e.n >= 4;
+    const float ema_w = w_dev ? *w_dev : w_arg;            // device-resident w: a captured graph replays with a new value
+    const bool ema_copy = ema_w >= 1.f;                    // (the same in every thread of the grid)
+    // (whole workgroup: nothing of this tensor is its to update; chunk 0 always stays, it owns the tail)
+    if ((long)blockIdx.x * blockDim.x * (vec ? 4 : 1) >= e.n) return;
+    const int t = threadIdx.x;
+    float A = a.A, B = a.B, bc1 = a.bc1, sbc2 = a.sbc2;
+    if (a.sched_dev) {
+        A = a.sched_dev[0];
+        B = a.sched_dev[1];
+        if constexpr (KIND == LEDN_OPTIM_ADAMW) {
+            bc1 = a.sched_dev[2];
+            sbc2 = a.sched_dev[3];
+        }
+    }
+    OptimConsts c;
+    c.gs = a.gscale;
+    if constexpr (CLIP == OPT_CLIP_L2 || CLIP == OPT_CLIP_INF) {
+        __shared__ float s_w[4];
+        float tot = block256_combine<CLIP == OPT_CLIP_INF>(t < a.n_partials ? a.partials[t] : 0.f, s_w);
+        if constexpr (CLIP == OPT_CLIP_L2) tot = sqrtf(tot);
+        tot *= a.gscale;                                   // the norm of the gradient the update uses (DDP's mean)
+        const float q = a.max_norm / (tot + 1e-6f);
+        const float coef = q > 1.f ? 1.f : q;              // torch.clamp(max=1): a NaN coefficient stays NaN
+        if (a.norm_out && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {
+            a.norm_out[0] = tot;
+            a.norm_out[1] = coef;
+        }
+        c.gs = a.gscale * coef;
+    }
+    c.cv = a.clip_value;
+    c.lr = e.lr_mult * A + B;
+    c.wd = e.wd_mult * a.weight_decay;
+    c.mom = a.momentum;
+    c.decay = 1.f - c.lr * c.wd;
+    c.b1 = a.b1, c.omb1 = a.omb1, c.b2 = a.b2, c.omb2 = a.omb2;
+    c.step = c.lr / bc1;
+    c.sbc2 = sbc2;
+    c.eps = a.eps;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long i0 = (long)blockIdx.x * blockDim.x + t;
+    if (vec) {
+        const long nvec = e.n >> 2;
+        float4* pv = reinterpret_cast<float4*>(e.p);
+        float4* gv = reinterpret_cast<float4*>(e.g);
+        float4* mv = reinterpret_cast<float4*>(e.m);
+        float4* vv = reinterpret_cast<float4*>(e.v);
+        for (long i = i0; i < nvec; i += stride) {
+            float4 p = pv[i], m = mv[i], v = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 g = gv[i];
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = vv[i];
+            optim_update<KIND, CLIP>(c, p.x, g.x, m.x, v.x);
+            optim_update<KIND, CLIP>(c, p.y, g.y, m.y, v.y);
+            optim_update<KIND, CLIP>(c, p.z, g.z, m.z, v.z);
+            optim_update<KIND, CLIP>(c, p.w, g.w, m.w, v.w);
+            mv[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) vv[i] = v;
+            pv[i] = p;
+            gv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            {
+                float4* av = reinterpret_cast<float4*>(avg);
+                float4 x = p;
+                if (!ema_copy) {
+                    x = av[i];
+                    x.x = ema_lerp(ema_w, x.x, p.x);
+                    x.y = ema_lerp(ema_w, x.y, p.y);
+                    x.z = ema_lerp(ema_w, x.z, p.z);
+                    x.w = ema_lerp(ema_w, x.w, p.w);
+                }
+                av[i] = x;
+            }
+        }
+        const long done = nvec << 2;
+        if (blockIdx.x == 0 && done + t < e.n) {
+            const long i = done + t;
+            float p = e.p[i], m = e.m[i], v = 0.f;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = e.v[i];
+            optim_update<KIND, CLIP>(c, p, e.g[i], m, v);
+            e.m[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) e.v[i] = v;
+            e.p[i] = p;
+            e.g[i] = 0.f;
+            avg[i] = ema_copy ? p : ema_lerp(ema_w, avg[i], p);
+        }
+    } else {
+        for (long i = i0; i < e.n; i += stride) {
+            float p = e.p[i], m = e.m[i], v = 0.f;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = e.v[i];
+            optim_update<KIND, CLIP>(c, p, e.g[i], m, v);
+            e.m[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) e.v[i] = v;
+            e.p[i] = p;
+            e.g[i] = 0.f;
+            avg[i] = ema_copy ? p : ema_lerp(ema_w, avg[i], p);
+        }
+    }
+}
+
 // (every table entry of an AdamW step needs a second-moment pointer; the table lives on the device, so the caller says
 // whether it filled them in: ledn_optim_desc.has_v)
-int optim_step_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d,
-                    hipStream_t s) {
+// avgs == NULL: ledn_optim_step (optim_kernel); else ledn_optim_step_ema (optim_ema_kernel, same grid)
+static int optim_launch(const ledn_optim_entry* table_dev, float* const* avgs, int n_tensors, long long max_n,
+                        const ledn_optim_desc* d, float ema_w, const float* ema_w_dev, hipStream_t s) {
     LEDN_REQUIRE(table_dev && d && n_tensors > 0 && max_n > 0);
     LEDN_REQUIRE(d->kind == LEDN_OPTIM_SGD || d->kind == LEDN_OPTIM_ADAMW);
     if (d->kind == LEDN_OPTIM_ADAMW) {
@@ -1264,7 +1375,11 @@ int optim_step_impl(const ledn_optim_entry* table_dev, int n_tensors, long long 
     long chunks = cdiv(max_n, 256 * 8);
     if (chunks > 64) chunks = 64;
     const dim3 grid((unsigned)chunks, (unsigned)n_tensors);
-#define LEDN_OPTIM(KIND, CLIP) LEDN_LAUNCH((optim_kernel<KIND, CLIP>), grid, dim3(256), 0, s, a)
+#define LEDN_OPTIM(KIND, CLIP)                                                                                  \
+    do {                                                                                                        \
+        if (avgs) LEDN_LAUNCH((optim_ema_kernel<KIND, CLIP>), grid, dim3(256), 0, s, a, avgs, ema_w, ema_w_dev); \
+        else LEDN_LAUNCH((optim_kernel<KIND, CLIP>), grid, dim3(256), 0, s, a);                                 \
+    } while (0)
 #define LEDN_OPTIM_KIND(KIND)                                        \
     switch (clip) {                                                  \
         case OPT_CLIP_L2: LEDN_OPTIM(KIND, OPT_CLIP_L2); break;      \
@@ -1275,6 +1390,71 @@ int optim_step_impl(const ledn_optim_entry* table_dev, int n_tensors, long long 
     if (d->kind == LEDN_OPTIM_SGD) { LEDN_OPTIM_KIND(LEDN_OPTIM_SGD) } else { LEDN_OPTIM_KIND(LEDN_OPTIM_ADAMW) }
 #undef LEDN_OPTIM_KIND
 #undef LEDN_OPTIM
+    return check_launch();
+}
+
+int optim_step_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d,
+                    hipStream_t s) {
+    return optim_launch(table_dev, nullptr, n_tensors, max_n, d, 0.f, nullptr, s);
+}
+
+int optim_step_ema_impl(const ledn_optim_entry* table_dev, float* const* avg_table_dev, int n_tensors, long long max_n,
+                        const ledn_optim_desc* d, float w, const float* w_dev, hipStream_t s) {
+    LEDN_REQUIRE(avg_table_dev);
+    LEDN_REQUIRE(w_dev || (w > 0.f && w <= 1.f));
+    return optim_launch(table_dev, avg_table_dev, n_tensors, max_n, d, w, w_dev, s);
+}
+
+// ===========================================================================
+// standalone multi-tensor weight averaging (ledn_ema_update): avg <- avg + w * (src - avg) over a table of {avg, src, n},
+// for what the optimizer launch does not touch (frozen parameters, parameters without a gradient, BatchNorm running
+// statistics).  grid, access rule, lerp and copy branch as optim_ema_kernel; no atomics, no reduction.
+// ===========================================================================
+__global__ void __launch_bounds__(256) ema_update_kernel(const ledn_ema_entry* table, float w_arg, const float* w_dev) {
+    const ledn_ema_entry e = table[blockIdx.y];
+    const bool vec = ((((uintptr_t)e.avg | (uintptr_t)e.src) & 15u) == 0) && e.n >= 4;
+    if ((long)blockIdx.x * blockDim.x * (vec ? 4 : 1) >= e.n) return;
+    const float w = w_dev ? *w_dev : w_arg;
+    const bool copy = w >= 1.f;
+    const int t = threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long i0 = (long)blockIdx.x * blockDim.x + t;
+    if (vec) {
+        const long nvec = e.n >> 2;
+        float4* av = reinterpret_cast<float4*>(e.avg);
+        const float4* sv = reinterpret_cast<const float4*>(e.src);
+        for (long i = i0; i < nvec; i += stride) {
+            const float4 p = sv[i];
+            float4 x = p;
+            if (!copy) {
+                x = av[i];
+                x.x = ema_lerp(w, x.x, p.x);
+                x.y = ema_lerp(w, x.y, p.y);
+                x.z = ema_lerp(w, x.z, p.z);
+                x.w = ema_lerp(w, x.w, p.w);
+            }
+            av[i] = x;
+        }
+        const long i = (nvec << 2) + t;
+        if (blockIdx.x == 0 && i < e.n) {
+            const float p = e.src[i];
+            e.avg[i] = copy ? p : ema_lerp(w, e.avg[i], p);
+        }
+    } else {
+        for (long i = i0; i < e.n; i += stride) {
+            const float p = e.src[i];
+            e.avg[i] = copy ? p : ema_lerp(w, e.avg[i], p);
+        }
+    }
+}
+
+int ema_update_impl(const ledn_ema_entry* table_dev, int n_tensors, long long max_n, float w, const float* w_dev,
+                    hipStream_t s) {
+    LEDN_REQUIRE(table_dev && n_tensors > 0 && max_n > 0);
+    LEDN_REQUIRE(w_dev || (w > 0.f && w <= 1.f));
+    long chunks = cdiv(max_n, 256 * 8);
+    if (chunks > 64) chunks = 64;
+    LEDN_LAUNCH(ema_update_kernel, dim3((unsigned)chunks, (unsigned)n_tensors), dim3(256), 0, s, table_dev, w, w_dev);
     return check_launch();
 }
 

@@ -149,6 +149,9 @@ int sgd_step_clip_impl(const ledn_sgd_entry* table_dev, int n_tensors, long long
                        float momentum, float weight_decay, float grad_scale, const float* partials, int n_partials,
                        int norm_type, float max_norm, float clip_value, float* norm_out, hipStream_t s);
 int optim_step_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d, hipStream_t s);
+int optim_step_ema_impl(const ledn_optim_entry* table_dev, float* const* avg_table_dev, int n_tensors, long long max_n,
+                        const ledn_optim_desc* d, float w, const float* w_dev, hipStream_t s);
+int ema_update_impl(const ledn_ema_entry* table_dev, int n_tensors, long long max_n, float w, const float* w_dev, hipStream_t s);
 }  // namespace ledn
 
 #include <mutex>
@@ -685,6 +688,14 @@ int ledn_sgd_step_clip(const ledn_sgd_entry* table_dev, int n_tensors, long long
 int ledn_optim_step(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d,
                     void* stream) {
     return optim_step_impl(table_dev, n_tensors, max_n, d, S(stream));
+}
+int ledn_optim_step_ema(const ledn_optim_entry* table_dev, float* const* avg_table_dev, int n_tensors, long long max_n,
+                        const ledn_optim_desc* d, float w, const float* w_dev, void* stream) {
+    return optim_step_ema_impl(table_dev, avg_table_dev, n_tensors, max_n, d, w, w_dev, S(stream));
+}
+int ledn_ema_update(const ledn_ema_entry* table_dev, int n_tensors, long long max_n, float w, const float* w_dev,
+                    void* stream) {
+    return ema_update_impl(table_dev, n_tensors, max_n, w, w_dev, S(stream));
 }
 
 }  // extern "C"

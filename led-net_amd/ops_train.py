@@ -948,19 +948,21 @@ def optim_scalars(lr_a, lr_b=0.0, betas=(0.9, 0.999), t=1):
 
 class OptimTable:
     """Device table of {param, grad, m, v, n, lr_mult, wd_mult} for ledn_optim_step: SGD (vs=None) or AdamW (vs = the
-    second moments, moms = the first) with one learning-rate and one weight-decay multiplier per tensor."""
+    second moments, moms = the first) with one learning-rate and one weight-decay multiplier per tensor.  avgs: one
+    averaged copy per parameter (EMAHook); the step is then ledn_optim_step_ema."""
 
-    def __init__(self, params, grads, moms, vs=None, lr_mults=None, wd_mults=None):
+    def __init__(self, params, grads, moms, vs=None, lr_mults=None, wd_mults=None, avgs=None):
         lib = _lib.get_lib()
         n = len(params)
         lr_mults = [1.0] * n if lr_mults is None else list(lr_mults)
         wd_mults = [1.0] * n if wd_mults is None else list(wd_mults)
-        if not (len(grads) == len(moms) == len(lr_mults) == len(wd_mults) == n and (vs is None or len(vs) == n)) or n == 0:
+        if not (len(grads) == len(moms) == len(lr_mults) == len(wd_mults) == n and (vs is None or len(vs) == n)
+                and (avgs is None or len(avgs) == n)) or n == 0:
             raise LednError('OptimTable: one gradient, state and multiplier per parameter')
         host = (_lib.OptimEntry * n)()
         self.max_n = 0
         for i, (p, g, m) in enumerate(zip(params, grads, moms)):
-            ts = (p, g, m) + ((vs[i],) if vs is not None else ())
+            ts = (p, g, m) + ((vs[i],) if vs is not None else ()) + ((avgs[i],) if avgs is not None else ())
             for t in ts:
                 if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
                     raise LednError('optimizer tensors must be contiguous float32 of the parameter\'s size')
@@ -975,12 +977,16 @@ class OptimTable:
         self.has_v = vs is not None
         self.keep = (params, grads, moms, vs)
         self.lr_mults, self.wd_mults = lr_mults, wd_mults
+        self.avgs, self.avg_table = avgs, None
+        if avgs is not None:
+            self.avg_table = torch.tensor([a.data_ptr() for a in avgs], dtype=torch.int64).to(params[0].device)
 
     def step(self, kind, lr_a, lr_b=0.0, *, momentum=0.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0,
-             t=1, sched_dev=None, clip=None):
+             t=1, sched_dev=None, clip=None, ema_w=None, ema_dev=None):
         """one launch.  kind: _lib.OPTIM_SGD / OPTIM_ADAMW; tensor i moves at lr_mults[i] * lr_a + lr_b with the decay
         wd_mults[i] * weight_decay; t: AdamW's 1-based step count; sched_dev: None or the four device floats
-        optim_scalars() describes (they then replace lr_a, lr_b and t); clip: as SgdTable.step."""
+        optim_scalars() describes (they then replace lr_a, lr_b and t); clip: as SgdTable.step.  A table with avgs
+        needs the averaging weight, ema_w (0 < w <= 1; 1 copies) or ema_dev (one device float, which wins)."""
         lib = _lib.get_lib()
         d = _lib.OptimDesc()
         d.kind, d.has_v = int(kind), int(self.has_v)
@@ -1002,7 +1008,55 @@ class OptimTable:
             d.norm_out = _p(clip.norm_out) if by_norm else None
         nel = sum(p.numel() for p in self.keep[0])
         work = _ops._TIMING is not None and (f'optim {self.n} tensors', (32 if self.has_v else 16) * nel, 0, 'optim_kernel')
-        _run(lib, 'ledn_optim_step', self.ref, self.table.data_ptr(), self.n, self.max_n, C.byref(d), work=work)
+        if (self.avgs is None) != (ema_w is None and ema_dev is None):
+            raise LednError('OptimTable.step: ema_w / ema_dev go with a table built with avgs, and such a table needs one')
+        if self.avgs is None:
+            _run(lib, 'ledn_optim_step', self.ref, self.table.data_ptr(), self.n, self.max_n, C.byref(d), work=work)
+            return
+        _check_ema_w(lib, ema_dev)
+        _run(lib, 'ledn_optim_step_ema', self.ref, self.table.data_ptr(), self.avg_table.data_ptr(), self.n, self.max_n,
+             C.byref(d), float(ema_w if ema_w is not None else 0.0), _p(ema_dev),
+             work=work and (work[0] + ' ema', work[1] + 8 * nel, 0, 'optim_ema_kernel'))
+
+
+def _check_ema_w(lib, ema_dev):
+    if ema_dev is not None:
+        if ema_dev.dtype != torch.float32 or ema_dev.numel() != 1:
+            raise LednError('ema_dev: one float32 value')
+        _check(lib, ema_dev)
+
+
+class EmaTable:
+    """Device table of {avg, src, n} for ledn_ema_update: the averaged copies of tensors the optimizer launch does not
+    touch (frozen parameters, parameters without a gradient, BatchNorm running statistics), one launch for all."""
+
+    def __init__(self, avgs, srcs):
+        lib = _lib.get_lib()
+        n = len(avgs)
+        if n == 0 or len(srcs) != n:
+            raise LednError('EmaTable: one source per averaged tensor')
+        host = (_lib.EmaEntry * n)()
+        self.max_n = 0
+        for i, (a, x) in enumerate(zip(avgs, srcs)):
+            for t in (a, x):
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.numel():
+                    raise LednError('averaged tensors must be contiguous float32 of their source\'s size')
+            _check(lib, a, x)
+            host[i].avg, host[i].src, host[i].n = a.data_ptr(), x.data_ptr(), x.numel()
+            self.max_n = max(self.max_n, x.numel())
+        self.table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(avgs[0].device)
+        self.n, self.ref, self.keep = n, avgs[0], (avgs, srcs)
+
+    def update(self, w=None, w_dev=None):
+        """avg <- avg + w * (src - avg), a copy for w >= 1; w_dev (one device float) wins over w"""
+        lib = _lib.get_lib()
+        if w is None and w_dev is None:
+            raise LednError('EmaTable.update: w or w_dev')
+        _check_ema_w(lib, w_dev)
+        work = _ops._TIMING is not None and (f'ema {self.n} tensors', 12 * sum(x.numel() for x in self.keep[1]), 0,
+                                             'ema_update_kernel')
+        _run(lib, 'ledn_ema_update', self.ref, self.table.data_ptr(), self.n, self.max_n,
+             float(w if w is not None else 0.0), _p(w_dev), work=work)
 
 
 def norm_partials_count(n):

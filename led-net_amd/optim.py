@@ -225,3 +225,61 @@ class Schedule:
             d.update({k: v for k, v in e.items() if k not in ('type', 'begin', 'end')})
             out.append(d)
         return out
+
+
+# --------------------------------------------------------------------------- #
+# custom_hooks = [dict(type='EMAHook', ema_type=, momentum=, update_buffers=, begin_iter=, interval=, gamma=), ...]
+# --------------------------------------------------------------------------- #
+_EMA_TYPES = {'ExponentialMovingAverage': set(), 'ExpMomentumEMA': {'gamma'}}
+_EMA_KEYS = {'type', 'ema_type', 'momentum', 'update_buffers', 'begin_iter', 'interval', 'priority'}
+
+
+def parse_ema_hook(custom_hooks):
+    """the config's custom_hooks list -> None (no EMAHook in it) or dict(ema_type, momentum, gamma, update_buffers,
+    begin_iter).  Hooks of other types are not this function's business and are skipped; inside the EMAHook entry every
+    key is honoured or raises ValueError (DESIGN.md "Weight averaging in the optimizer step")."""
+    if not custom_hooks:
+        return None
+    if not isinstance(custom_hooks, (list, tuple)):
+        raise ValueError(f'custom_hooks must be a list of dicts, got {type(custom_hooks).__name__}')
+    hooks = [h for h in custom_hooks if isinstance(h, dict) and h.get('type') == 'EMAHook']
+    if not hooks:
+        return None
+    if len(hooks) > 1:
+        raise ValueError('custom_hooks: more than one EMAHook')
+    h = hooks[0]
+    for key in ('strict_load', 'begin_epoch'):
+        if key in h:
+            raise ValueError(f'EMAHook: {key} is not supported' + (' (the schedule runs by iteration: use begin_iter)'
+                                                                   if key == 'begin_epoch' else ''))
+    ema_type = h.get('ema_type', 'ExponentialMovingAverage')
+    if ema_type not in _EMA_TYPES:
+        raise ValueError(f"EMAHook: ema_type={ema_type!r} is not supported (supported: 'ExponentialMovingAverage', "
+                         f"'ExpMomentumEMA')")
+    unknown = sorted(set(h) - _EMA_KEYS - _EMA_TYPES[ema_type])
+    if unknown:
+        raise ValueError(f'EMAHook (ema_type={ema_type!r}): unknown key {unknown[0]!r}')
+    if h.get('interval', 1) != 1:
+        raise ValueError(f'EMAHook: interval={h["interval"]!r} is not supported (only 1: the update is part of every '
+                         f'optimizer launch)')
+    momentum = h.get('momentum', 0.0002)
+    if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0.0 < momentum < 1.0:
+        raise ValueError(f'EMAHook: momentum={momentum!r} must be in (0, 1)')
+    begin_iter = h.get('begin_iter', 0)
+    if isinstance(begin_iter, bool) or not isinstance(begin_iter, int) or begin_iter < 0:
+        raise ValueError(f'EMAHook: begin_iter={begin_iter!r} must be a non-negative integer')
+    gamma = None
+    if ema_type == 'ExpMomentumEMA':
+        gamma = h.get('gamma', 2000)
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not gamma > 0:
+            raise ValueError(f'EMAHook: gamma={gamma!r} must be > 0')
+    return dict(ema_type=ema_type, momentum=float(momentum), gamma=gamma, update_buffers=bool(h.get('update_buffers', False)),
+                begin_iter=begin_iter)
+
+
+def ema_weight(ema, steps):
+    """the averaging weight w of the update that follows `steps` finished ones (steps >= 1), formed in double"""
+    m = ema['momentum']
+    if ema['ema_type'] == 'ExpMomentumEMA':
+        return (1.0 - m) * math.exp(-(1.0 + steps) / ema['gamma']) + m
+    return m

@@ -9,6 +9,7 @@ OptimWrapper.update_params (backward + SGD step); SyncBN / DDP collectives are
 implicit there and explicit here (RCCL via
 torch.distributed on the [2,C] statistic buffers and the flat gradient buffer).
 """
+import contextlib
 import math
 import os as _os
 
@@ -1540,7 +1541,7 @@ class Trainer:
 
     def __init__(self, model, cfg=None, world_size=1, lr=None, momentum=None, weight_decay=None,
                  max_iters=None, power=0.9, eta_min=0.0, bucket_mb=2.0, direct_grads=True, collectives=None,
-                 clip_grad=None, paramwise_cfg=None):
+                 clip_grad=None, paramwise_cfg=None, ema=None):
         # config: optim_wrapper = dict(type='OptimWrapper', optimizer=..., clip_grad=..., paramwise_cfg=...); a config
         # without that section keeps its optimizer at the top level.  (optim.py / DESIGN.md "Optimizer construction
         # from the config": every key is honoured or raises ValueError.)
@@ -1561,9 +1562,12 @@ class Trainer:
         first = self.sched.entries[0]       # (a lone PolyLR: the two numbers older callers read)
         self.power, self.eta_min = first.get('power', power), first.get('eta_min', eta_min)
         self.paramwise = pw
+        # weight averaging (custom_hooks' EMAHook; ema=: the result of optim.parse_ema_hook, which wins)
+        self.ema = ema if ema is not None else O.parse_ema_hook((cfg or {}).get('custom_hooks'))
         # plain SGD under a lone PolyLR keeps the ledn_sgd_step(_clip) launch; everything else -- AdamW, per-parameter
-        # multipliers, a scheduler list -- is ONE ledn_optim_step launch over the extended table
-        self._general = not (self.opt_kind == 'SGD' and pw is None and self.sched.lone_poly)
+        # multipliers, a scheduler list, weight averaging -- is ONE ledn_optim_step(_ema) launch over the extended table
+        self._plain = self.opt_kind == 'SGD' and pw is None and self.sched.lone_poly
+        self._general = not self._plain or self.ema is not None
         self.iter = 0
         self.world = world_size
         # gradient layout: [stem | everything else], each in module order.  The stem's backward comes LAST (and is
@@ -1587,6 +1591,29 @@ class Trainer:
             if self.flat_v is not None:
                 self.vs.append(self.flat_v[off:off + k].view_as(p))
             off += k
+        # averaged weights: ONE flat f32 buffer, [laid out like flat_mom | frozen parameters | floating-point buffers
+        # (update_buffers=True)], starting as a copy of the model (as mmengine's averaged model does)
+        self.flat_ema, self.emas, self.ema_steps, self._ema_dev, self._ema_table = None, [], 0, None, None
+        self._ema_extra = []                 # (name, source tensor, averaged view) of what follows the flat_mom layout
+        if self.ema is not None:
+            extra = [(n_, p) for n_, p in model.named_parameters() if not p.requires_grad]
+            if self.ema['update_buffers']:
+                extra += [(n_, b) for n_, b in model.named_buffers() if b.is_floating_point()]
+            for _, t in extra:
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError('EMAHook: averaged tensors must be contiguous float32')
+            self.flat_ema = torch.empty(n + sum(t.numel() for _, t in extra), dtype=torch.float32, device=dev)
+            off = 0
+            with torch.no_grad():
+                for p in self.params:
+                    self.emas.append(self.flat_ema[off:off + p.numel()].view_as(p))
+                    self.emas[-1].copy_(p)
+                    off += p.numel()
+                for n_, t in extra:
+                    self._ema_extra.append((n_, t, self.flat_ema[off:off + t.numel()].view_as(t)))
+                    self._ema_extra[-1][2].copy_(t)
+                    off += t.numel()
+            self._ema_dev = torch.ones(1, dtype=torch.float32, device=dev)      # w of the next update (1: copy)
         mults = O.paramwise_multipliers(model, pw) if pw is not None else {}
         self.names = [n_ for n_, _ in late] + [n_ for n_, _ in early]
         self.mults = [mults.get(name, (1.0, 1.0)) for name in self.names]      # (lr_mult, decay_mult) per parameter
@@ -1625,6 +1652,8 @@ class Trainer:
             for b in model.buffers():
                 if b.is_floating_point():
                     dist.broadcast(b.data, 0)
+            if self.ema is not None:
+                self.load_ema_state(0, {})              # the average starts from the weights every rank now holds
         if mode in ('auto', 'rccl') and dev.type == 'cuda' and (world_size > 1 or mode == 'rccl'):
             try:
                 from . import rccl
@@ -1773,11 +1802,79 @@ class Trainer:
 
     def _optim_scalars(self):
         """{A, B, bc1, sqrt(bc2)} of this iteration for ledn_optim_step (AdamW's 1-based step count = iter + 1)"""
-        a, b = self.sched.scalars(self.base_lr, self.iter)
+        if self._plain:             # (a plain SGD configuration routed here by the EMAHook: the rate ledn_sgd_step gets)
+            a, b = self.lr(), 0.0
+        else:
+            a, b = self.sched.scalars(self.base_lr, self.iter)
         return T.optim_scalars(a, b, self.betas, self.iter + 1)
 
+    # ------------------------------------------------------------------ #
+    # weight averaging (EMAHook)
+    def _ema_w(self):
+        """the averaging weight of this iteration's update; 1 = exact copy (before begin_iter, and the first update)"""
+        if self.iter < self.ema['begin_iter'] or self.ema_steps == 0:
+            return 1.0
+        return O.ema_weight(self.ema, self.ema_steps)
+
+    def _ema_tick(self):
+        """host side of one finished update (call before self.iter moves on)"""
+        if self.ema is not None and self.iter >= self.ema['begin_iter']:
+            self.ema_steps += 1
+
+    def _ema_named(self):
+        """(state_dict key, model tensor, averaged view) of everything the averaged model holds on its own"""
+        names = {id(p): n_ for n_, p in self.model.named_parameters()}
+        return [(names[id(p)], p, a) for p, a in zip(self.params, self.emas)] + list(self._ema_extra)
+
+    def ema_state(self):
+        """-> dict(steps=, state_dict=): the averaged model's state_dict on the CPU.  What it does not hold on its own
+        (every buffer without update_buffers, integer buffers always) is the training model's."""
+        assert self.ema is not None, 'this trainer runs no EMAHook'
+        sd = {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}
+        for name, _, a in self._ema_named():
+            if name in sd:
+                sd[name] = a.detach().cpu().clone()
+        return dict(steps=int(self.ema_steps), state_dict=sd)
+
+    def load_ema_state(self, steps, state_dict):
+        """restore the counter and the averaged weights (state_dict: the model's keys; a missing key keeps the current
+        value of the model's tensor)"""
+        assert self.ema is not None, 'this trainer runs no EMAHook'
+        with torch.no_grad():
+            for name, t, a in self._ema_named():
+                src = state_dict.get(name)
+                a.copy_((src if src is not None else t.detach()).to(a.device, torch.float32).view_as(a))
+        self.ema_steps = int(steps)
+
+    def _ema_swap(self):
+        with torch.no_grad():
+            for _, t, a in self._ema_named():
+                tmp = t.detach().clone()
+                t.copy_(a)
+                a.copy_(tmp)
+        for m in self.model.modules():      # derived caches (folded BN, bf16 weight packs) belong to the other weights
+            cache = getattr(m, '_cache', None)
+            if isinstance(cache, dict):
+                cache.clear()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """the hook's before / after validation: inside, the model holds the averaged weights (swapped by content with
+        device copies: every pointer a captured graph recorded stays valid); on exit they are swapped back bit-exactly"""
+        assert self.ema is not None, 'this trainer runs no EMAHook'
+        self._ema_swap()
+        try:
+            yield self.model
+        finally:
+            self._ema_swap()
+
     def _refresh_dev(self):
-        """the device-resident scalars a captured graph reads: the rate (plain SGD) or {A, B, bc1, sqrt(bc2)}"""
+        """the device-resident scalars a captured graph reads: the rate (plain SGD) or {A, B, bc1, sqrt(bc2)}, and the
+        averaging weight"""
+        if self._ema_dev is not None:
+            self._ema_dev.fill_(self._ema_w())
+        if self._lr_dev is None:
+            return
         if not self._general:
             self._lr_dev.fill_(self.lr())
             return
@@ -1917,7 +2014,14 @@ class Trainer:
             if self._general:
                 self.table = T.OptimTable(self.live, self.live_views, [self.moms[i] for i in idx],
                                           [self.vs[i] for i in idx] if self.flat_v is not None else None,
-                                          [self.mults[i][0] for i in idx], [self.mults[i][1] for i in idx])
+                                          [self.mults[i][0] for i in idx], [self.mults[i][1] for i in idx],
+                                          avgs=[self.emas[i] for i in idx] if self.ema is not None else None)
+                if self.ema is not None:
+                    # what the optimizer launch does not touch: parameters without a gradient, frozen parameters and
+                    # (update_buffers=True) the running statistics -- one ledn_ema_update launch behind it
+                    rest = [(a, p.detach()) for p, a in zip(self.params, self.emas) if p.grad is None]
+                    rest += [(a, t.detach()) for _, t, a in self._ema_extra]
+                    self._ema_table = T.EmaTable([a for a, _ in rest], [t for _, t in rest]) if rest else None
             else:
                 self.table = T.SgdTable(self.live, self.live_views, [self.moms[i] for i in idx])
             if self.direct_grads:
@@ -1949,7 +2053,8 @@ class Trainer:
             self._exchange(0, self.n_late if self._early_done else self.flat_grad.numel())
             if self._gstream is not None:
                 torch.cuda.current_stream(self.flat_grad.device).wait_stream(self._gstream)
-        if self._lr_dev is not None and not torch.cuda.is_current_stream_capturing():
+        if (self._lr_dev is not None or self._ema_dev is not None) and not (
+                self.flat_grad.is_cuda and torch.cuda.is_current_stream_capturing()):
             self._refresh_dev()                 # eager step after a capture(): keep the device-resident rate current
         if self.clip is not None:
             # after the exchange (and the wait for its stream): the norm of the all-reduced gradient, the same on every rank
@@ -1958,11 +2063,14 @@ class Trainer:
             a, b, _, _ = self._optim_scalars()
             self.table.step(_lib.OPTIM_ADAMW if self.opt_kind == 'AdamW' else _lib.OPTIM_SGD, a, b, momentum=self.momentum,
                             betas=self.betas, eps=self.eps, weight_decay=self.wd, grad_scale=1.0 / self.world,
-                            t=self.iter + 1, sched_dev=self._lr_dev, clip=self.clip)
+                            t=self.iter + 1, sched_dev=self._lr_dev, clip=self.clip, ema_dev=self._ema_dev)
+            if self._ema_table is not None:
+                self._ema_table.update(w_dev=self._ema_dev)
         elif self.clip is None:
             self.table.step(self.lr(), self.momentum, self.wd, 1.0 / self.world, lr_dev=self._lr_dev)
         else:
             self.table.step(self.lr(), self.momentum, self.wd, 1.0 / self.world, lr_dev=self._lr_dev, clip=self.clip)
+        self._ema_tick()
         self.iter += 1
         # detached: a caller holding the returned losses would otherwise keep the step's autograd graph
         # (and its AccumulateGrad nodes, bound to this step's stream) alive into a later hipGraph capture,
@@ -2004,7 +2112,8 @@ class Trainer:
         if restore:
             snap = ([p.detach().clone() for p in self.params], self.flat_mom.clone(),
                     [b.detach().clone() for b in self.model.buffers()], self.iter,
-                    self.flat_v.clone() if self.flat_v is not None else None)
+                    self.flat_v.clone() if self.flat_v is not None else None,
+                    self.flat_ema.clone() if self.flat_ema is not None else None, self.ema_steps)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -2020,16 +2129,20 @@ class Trainer:
                         self.flat_v.copy_(snap[4])
                     for b, v in zip(self.model.buffers(), snap[2]):
                         b.copy_(v)
-                self.iter = snap[3]
+                    if self.flat_ema is not None:
+                        self.flat_ema.copy_(snap[5])
+                self.iter, self.ema_steps = snap[3], snap[6]
         torch.cuda.current_stream(dev).wait_stream(side)
         self._refresh_dev()
         self._graph = torch.cuda.CUDAGraph()
         # N > 1: other threads of the process (ProcessGroupNCCL's watchdog) keep calling the runtime while this
         # thread captures; 'thread_local' confines the capture-safety checks to the capturing thread
         mode = _os.environ.get('LEDN_CAPTURE_MODE') or ('thread_local' if self.dist is not None else 'global')
+        steps = self.ema_steps
         with torch.cuda.graph(self._graph, capture_error_mode=mode):
             self._static_out = self.train_step(self._static_in, self._static_samples)
         self.iter -= 1          # capturing records the step, it does not execute it (PolyLR stays in step)
+        self.ema_steps = steps
         return self
 
     def replay(self, inputs=None, data_samples=None):
@@ -2056,6 +2169,7 @@ class Trainer:
                     self.model._valid_static.copy_(ext.to(self.model._valid_static.device))
         self._refresh_dev()
         self._graph.replay()
+        self._ema_tick()
         self.iter += 1
         return self._static_out
 

@@ -2,7 +2,10 @@
 """Training entry point with the reference's command line (tools/train.py:15-60: CONFIG, --work-dir,
 --resume, --amp, --cfg-options, --launcher, --local_rank) on the built-in loop: config's SGD + PolyLR,
 OhemCrossEntropy x2, SyncBN when launched with --launcher pytorch (one process per GPU, RCCL), loss line
-every 50 iterations, checkpoints in mmengine layout (iter_N.pth).  Datasets/augmentation are out of scope
+every 50 iterations, checkpoints in mmengine layout (iter_N.pth).  custom_hooks=[dict(type='EMAHook', ...)] in the
+config (or --cfg-options custom_hooks="[{'type':'EMAHook','momentum':0.001}]") switches weight averaging on: the
+Trainer reads it, the checkpoints then hold the averaged weights in 'state_dict' and the training weights in
+'ema_state_dict', and --resume undoes that swap.  Datasets/augmentation are out of scope
 (SURVEY.md section 2): batches are synthetic Cityscapes-shaped uint8 images with a 16-px ignore border.
 
     python tools/train.py CONFIG [--work-dir DIR] [--max-iters N] [--batch-size B] [--resume]
@@ -88,7 +91,8 @@ def main():
     model.to(dev)
     trainer = L.Trainer(model, cfg, world_size=world, max_iters=None)
     if ckpt is not None:
-        L.resume(trainer, ckpt)           # momentum buffers + PolyLR position (mmengine 'optimizer' / 'param_schedulers')
+        L.resume(trainer, ckpt)           # momentum buffers + PolyLR position (mmengine 'optimizer' / 'param_schedulers'),
+        # and with an EMAHook the averaged weights / training weights of 'ema_state_dict'
     trainer.iter = start
     max_iters = args.max_iters or trainer.max_iters
     bs = args.batch_size
