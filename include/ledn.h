@@ -864,6 +864,54 @@ int ledn_dice_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W,
                           void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * FocalLoss (sigmoid form, mmseg/models/losses/focal_loss.py:13-68,199-323: the branch FocalLoss.forward takes on the
+ * GPU) and TverskyLoss (tversky_loss.py:13-123), in the same two families and with the same layout, limits, out[0],
+ * out[1] (accuracy over the pixels whose label is not ignore_index resp. acc_ignore_index) and bit-reproducibility as
+ * the CE / Dice entry points above; out[2] = out[3] = 0.
+ * Focal: per pixel and class c, t = (label == c) (all zero for a label outside [0, C) that is not ignore_index),
+ * z = t ? -x : x, so that 1 - p_t = sigmoid(z) and -log p_t = softplus(z) (never log(sigmoid)):
+ *   l = class_weight[c] * (label != ignore_index) * (t ? a_c : 1 - a_c) * sigmoid(z)^gamma * softplus(z)
+ * a_c = alpha_v[c] (alpha_v [C] f32 on the device) or the scalar alpha (alpha_v NULL); class_weight [C] or NULL.
+ * out[0] = loss_weight * sum l / (N*HW*C) ('mean': ignored pixels stay in the divisor) or loss_weight * sum l ('sum').
+ * work: ledn_seg_loss_work_floats(N) floats.  The backward re-forms sigmoid and softplus from the logits; its scale is
+ * dloss * loss_weight / (N*HW*C) (resp. / 1).  gamma >= 0.
+ * Tversky: p = softmax, t = onehot(clamp(label, 0, C-1)), v = (label != ignore_index): the loss's OWN ignore_index,
+ * which also names the class left out of the loss.  Per image n and class i:
+ *   TP = sum p t v, FP = sum p (1-t) v, FN = sum (1-p) t v, T = (TP + smooth) / (TP + alpha FP + beta FN + smooth)
+ *   out[0] = loss_weight / C * sum_{i != ignore_index} class_weight[i] * mean_n (1 - T)
+ * smooth >= 0.  smooth == 0 is taken as given, as the reference takes it: an (image, class) with TP = FP = FN = 0 (every
+ * pixel of the image masked, say) then has a 0 / 0 term, and out[0] and that pair's backward coefficients are NaN.
+ * 2 <= C <= 32 (LEDN_EINVAL above).  work: ledn_tversky_work_floats(N, C) floats; after the forward
+ * work[(n*C + i)*5 .. +4] = TP, FP, FN and the backward's two coefficients dL/dp_i for t = 1 and t = 0 (without
+ * dloss).  The backward needs ignore_index (for v) and work only. */
+int ledn_focal_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C,
+                        const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                        int reduction, float loss_weight, float* work, float* out, void* stream);
+int ledn_focal_loss_bwd(const float* logits, const long long* target, int N, long long HW, int C,
+                        const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                        int reduction, float loss_weight, const float* work, const float* out, const float* dloss,
+                        float* dlogits, void* stream);
+int ledn_focal_loss_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                           const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                           int reduction, float loss_weight, float* work, float* out, void* stream);
+int ledn_focal_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                           const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                           int reduction, float loss_weight, const float* work, const float* out, const float* dloss,
+                           float* dsrc, void* stream);
+long long ledn_tversky_work_floats(long long N, int C);
+int ledn_tversky_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C,
+                          const float* class_weight, float alpha, float beta, float smooth, int ignore_index,
+                          int acc_ignore_index, float loss_weight, float* work, float* out, void* stream);
+int ledn_tversky_loss_bwd(const float* logits, const long long* target, int N, long long HW, int C, int ignore_index,
+                          const float* work, const float* out, const float* dloss, float* dlogits, void* stream);
+int ledn_tversky_loss_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                             const float* class_weight, float alpha, float beta, float smooth, int ignore_index,
+                             int acc_ignore_index, float loss_weight, float* work, float* out, void* stream);
+int ledn_tversky_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                             int ignore_index, const float* work, const float* out, const float* dloss, float* dsrc,
+                             void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The four pooled-context MLPs of Muti_AFF (classification/model_utils.py:377-400: AdaptiveAvgPool2d(S) ->
  * Conv1x1(C->Ci)+bias -> BatchNorm -> ReLU -> Conv1x1(Ci->C)+bias -> [BatchNorm: in the gate kernel], S = 4, 8, 16, 1)
  * as ONE launch sequence for all four scales: they are chains of tiny launch-bound kernels (~50 launches per

@@ -128,6 +128,7 @@ int ohem_ce_bwd_impl(const float* logits, const long long* target, long long P, 
                      const float* work, const float* out, const float* dloss, float loss_weight,
                      const float* cw, float* dlogits, hipStream_t s);
 long long seg_loss_work_floats(long long N);
+long long tversky_work_floats(long long N, int C);
 int seg_loss_fwd_impl(int kind, const float* logits, const long long* target, int N, long long HW, int C, const SlCfg& q,
                       float* work, float* out, hipStream_t s);
 int seg_loss_bwd_impl(int kind, const float* logits, const long long* target, int N, long long HW, int C, const SlCfg& q,
@@ -668,6 +669,73 @@ int ledn_dice_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W,
                           void* stream) {
     return seg_loss_up_bwd_impl(use_sigmoid ? SL_DICE_SIGMOID : SL_DICE_SOFTMAX, src, N, Hs, Ws, H, W, target,
                                 sl_dice_cfg(naive_dice, ignore_class, -1, reduction, eps, loss_weight), work, out, dloss, dsrc,
+                                S(stream));
+}
+static SlCfg sl_focal_cfg(const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                          int reduction, float loss_weight) {
+    SlCfg q = {class_weight, ignore_index, -1, 0, reduction, 0, 0.f, loss_weight, alpha_v, gamma, alpha, 0.f, 1.f};
+    return q;
+}
+static SlCfg sl_tversky_cfg(const float* class_weight, float alpha, float beta, float smooth, int ignore_index,
+                            int acc_ignore_index, float loss_weight) {
+    SlCfg q = {class_weight, acc_ignore_index, ignore_index, 0, 0, 0, smooth, loss_weight, nullptr, 0.f, alpha, beta, 1.f};
+    return q;
+}
+int ledn_focal_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C,
+                        const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                        int reduction, float loss_weight, float* work, float* out, void* stream) {
+    return seg_loss_fwd_impl(SL_FOCAL, logits, target, N, HW, C,
+                             sl_focal_cfg(class_weight, alpha_v, alpha, gamma, ignore_index, reduction, loss_weight), work,
+                             out, S(stream));
+}
+int ledn_focal_loss_bwd(const float* logits, const long long* target, int N, long long HW, int C,
+                        const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                        int reduction, float loss_weight, const float* work, const float* out, const float* dloss,
+                        float* dlogits, void* stream) {
+    return seg_loss_bwd_impl(SL_FOCAL, logits, target, N, HW, C,
+                             sl_focal_cfg(class_weight, alpha_v, alpha, gamma, ignore_index, reduction, loss_weight), work,
+                             out, dloss, dlogits, S(stream));
+}
+int ledn_focal_loss_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                           const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                           int reduction, float loss_weight, float* work, float* out, void* stream) {
+    return seg_loss_up_fwd_impl(SL_FOCAL, src, N, Hs, Ws, H, W, target,
+                                sl_focal_cfg(class_weight, alpha_v, alpha, gamma, ignore_index, reduction, loss_weight),
+                                work, out, S(stream));
+}
+int ledn_focal_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                           const float* class_weight, const float* alpha_v, float alpha, float gamma, int ignore_index,
+                           int reduction, float loss_weight, const float* work, const float* out, const float* dloss,
+                           float* dsrc, void* stream) {
+    return seg_loss_up_bwd_impl(SL_FOCAL, src, N, Hs, Ws, H, W, target,
+                                sl_focal_cfg(class_weight, alpha_v, alpha, gamma, ignore_index, reduction, loss_weight),
+                                work, out, dloss, dsrc, S(stream));
+}
+long long ledn_tversky_work_floats(long long N, int C) { return tversky_work_floats(N, C); }
+int ledn_tversky_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C,
+                          const float* class_weight, float alpha, float beta, float smooth, int ignore_index,
+                          int acc_ignore_index, float loss_weight, float* work, float* out, void* stream) {
+    return seg_loss_fwd_impl(SL_TVERSKY, logits, target, N, HW, C,
+                             sl_tversky_cfg(class_weight, alpha, beta, smooth, ignore_index, acc_ignore_index, loss_weight),
+                             work, out, S(stream));
+}
+int ledn_tversky_loss_bwd(const float* logits, const long long* target, int N, long long HW, int C, int ignore_index,
+                          const float* work, const float* out, const float* dloss, float* dlogits, void* stream) {
+    return seg_loss_bwd_impl(SL_TVERSKY, logits, target, N, HW, C, sl_tversky_cfg(nullptr, 0.f, 0.f, 0.f, ignore_index, -1, 1.f),
+                             work, out, dloss, dlogits, S(stream));
+}
+int ledn_tversky_loss_up_fwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                             const float* class_weight, float alpha, float beta, float smooth, int ignore_index,
+                             int acc_ignore_index, float loss_weight, float* work, float* out, void* stream) {
+    return seg_loss_up_fwd_impl(SL_TVERSKY, src, N, Hs, Ws, H, W, target,
+                                sl_tversky_cfg(class_weight, alpha, beta, smooth, ignore_index, acc_ignore_index, loss_weight),
+                                work, out, S(stream));
+}
+int ledn_tversky_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
+                             int ignore_index, const float* work, const float* out, const float* dloss, float* dsrc,
+                             void* stream) {
+    return seg_loss_up_bwd_impl(SL_TVERSKY, src, N, Hs, Ws, H, W, target,
+                                sl_tversky_cfg(nullptr, 0.f, 0.f, 0.f, ignore_index, -1, 1.f), work, out, dloss, dsrc,
                                 S(stream));
 }
 int ledn_sgd_step(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,

@@ -429,15 +429,22 @@ int head_mc_wgrad(const ledn_wgrad_desc& d, hipStream_t s);
 int channel_stats_fast(const void* x, const void* xadd, long long P, int C, int dtype, float* sum, float* sqsum,
                        hipStream_t s);
 // seg_loss.hip: the loss of a ledn_ce_loss_* / ledn_dice_loss_* call and its settings
-enum { SL_CE = 0, SL_DICE_SIGMOID = 1, SL_DICE_SOFTMAX = 2 };
+enum { SL_CE = 0, SL_DICE_SIGMOID = 1, SL_DICE_SOFTMAX = 2, SL_FOCAL = 3, SL_TVERSKY = 4 };
+constexpr int SL_TV_MAX_C = 32;      // Tversky: the most classes (the range the class heads are built for)
 struct SlCfg {
-    const float* cw;        // CE: class weights [C] on the device or null
-    int ignore_index;       // the label that takes no part in the accuracy (CE: nor in the loss)
-    int ignore_class;       // Dice: the dropped class channel (outside [0, C): none)
+    const float* cw;        // CE, Focal, Tversky: class weights [C] on the device or null
+    int ignore_index;       // the label that takes no part in the accuracy (CE, Focal: nor in the loss)
+    int ignore_class;       // Dice: the dropped class channel (outside [0, C): none); Tversky: its own ignore_index,
+                            // the label masked out of the sums AND the class left out of the loss
     int naive;              // Dice: first powers in the denominator
     int reduction;          // 0 mean, 1 sum
     int avg_non_ignore;     // CE
-    float eps, loss_weight;
+    float eps, loss_weight; // eps: Dice's eps, Tversky's smooth
+    // Focal / Tversky (zero for the others)
+    const float* alpha_v;   // Focal: per-class alpha [C] on the device or null (then the scalar)
+    float gamma;            // Focal
+    float alpha, beta;      // Focal: alpha; Tversky: the weights of FP and FN
+    float div;              // Focal: the divisor of the sum (N*HW*C for 'mean', 1 for 'sum'), set by the host side
 };
 
 }  // namespace ledn

@@ -25,6 +25,22 @@
 // Dice: the one-hot target is clamp(label, 0, C) with row C dropped (dice_loss.py:24-29): a label >= C (255 = ignored)
 // has target 0 in every class and still adds its p to the denominator, a negative label counts as class 0.
 // ignore_class is the reference's class-CHANNEL drop (dice_loss.py:69-72).
+//
+// FocalLoss (sigmoid form, focal_loss.py:13-68 on the flattening, one-hot and valid_mask of FocalLoss.forward's GPU
+// branch, :241-284) rides the same kernels as a further KIND: per pixel and class, z = t ? -x : x, so that
+// 1 - p_t = sigmoid(z) and -log p_t = softplus(z) = max(z, 0) + log1p(exp(-|z|)) (never log(sigmoid));
+// sigmoid(z)^gamma = exp(gamma * log sigmoid(z)), log sigmoid(z) = min(z, 0) - log1p(exp(-|z|)): no pow, and gamma = 0
+// gives exactly 1.  part: f0 = sum of the weighted elements; the finish divides by q.div (N*HW*C or 1).
+//
+// TverskyLoss (tversky_loss.py:13-123) needs three sums per (image, class), so its forward has kernels of its own
+// (tv_*): a thread keeps 3 x CB accumulators in registers for CB classes per pass (CB = 2 for two classes, else 8: the
+// pixel loop runs ceil(C / 8) times, re-forming the softmax, instead of 3 x 32 accumulators spilling to scratch).
+// work layout (ledn_tversky_work_floats(N, C) = 5 N C + max(SL_GRID, N) (2 + 3 C)):
+//   hdr[N][C][5] | cnt[N * G][2] | part[N * G][C][3]
+//   hdr (written by the finish): TP, FP, FN, and the backward's dL/dp_i for t = 1 and for t = 0 (without dloss)
+//   cnt (per workgroup, u32 bit patterns): #pixels with label != ignore_index, #of those whose argmax is the label
+//   part (per workgroup): TP, FP, FN of each class
+// Its backward is a KIND of the shared backward kernels: the 2 C coefficients of the image, times dloss, sit in LDS.
 #include "ledn_rt.h"
 
 namespace ledn {
@@ -51,6 +67,31 @@ struct SlAcc {
     unsigned u0, u1, u2;
 };
 
+// Focal: L = log1p(exp(-|z|)), so that softplus(z) = max(z, 0) + L and log sigmoid(z) = min(z, 0) - L
+__device__ __forceinline__ float sl_focal_alpha(const SlCfg& q, int c, bool t) {
+    const float a = q.alpha_v ? q.alpha_v[c] : q.alpha;
+    return (q.cw ? q.cw[c] : 1.f) * (t ? a : 1.f - a);
+}
+__device__ __forceinline__ float sl_focal_fwd(float x, bool t, int c, const SlCfg& q) {
+    const float z = t ? -x : x;
+    const float L = log1pf(__expf(-fabsf(z)));
+    const float sp = fmaxf(z, 0.f) + L;
+    const float mod = __expf(q.gamma * (fminf(z, 0.f) - L));
+    return sl_focal_alpha(q, c, t) * mod * sp;
+}
+// d/dx of the above times k: d mod / dz = gamma mod (1 - s), d sp / dz = s, s = sigmoid(z), dz/dx = -+1
+__device__ __forceinline__ float sl_focal_bwd(float x, bool t, int c, const SlCfg& q, float k) {
+    const float z = t ? -x : x;
+    const float e = __expf(-fabsf(z));
+    const float L = log1pf(e);
+    const float sp = fmaxf(z, 0.f) + L;
+    const float mod = __expf(q.gamma * (fminf(z, 0.f) - L));
+    const float r = 1.f / (1.f + e);
+    const float s = z >= 0.f ? r : e * r, s1 = z >= 0.f ? e * r : r;          // sigmoid(z), 1 - sigmoid(z)
+    const float g = k * sl_focal_alpha(q, c, t) * mod * (q.gamma * s1 * sp + s);
+    return t ? -g : g;
+}
+
 // one pixel of the forward: lg[C] logits, tg its label
 template <int KIND>
 __device__ __forceinline__ void sl_pixel_fwd(const float* lg, int C, long long tg, const SlCfg& q, SlAcc& a) {
@@ -62,7 +103,10 @@ __device__ __forceinline__ void sl_pixel_fwd(const float* lg, int C, long long t
         ++a.u1;
         if (am == tg) ++a.u2;
     }
-    if constexpr (KIND == SL_CE) {
+    if constexpr (KIND == SL_FOCAL) {
+        if (tg == q.ignore_index) return;
+        for (int c = 0; c < C; ++c) a.f0 += sl_focal_fwd(lg[c], c == tg, c, q);
+    } else if constexpr (KIND == SL_CE) {
         if (tg == q.ignore_index || tg < 0 || tg >= C) return;
         float se = 0.f;
         for (int c = 0; c < C; ++c) se += __expf(lg[c] - mx);
@@ -93,11 +137,29 @@ __device__ __forceinline__ void sl_pixel_fwd(const float* lg, int C, long long t
 
 // one pixel of the backward -> dl[C].  CE: k_t = dloss * loss_weight / divisor.  Dice: dL/dp_c = k_t t_c + k_p p_c
 // (naive: k_t t_c + k_p) on the kept classes, both already scaled by loss_weight * dloss (/ N), pulled through the
-// sigmoid or softmax Jacobian.
+// sigmoid or softmax Jacobian.  Focal: k_t = dloss * loss_weight / divisor.  Tversky: tv[2 c], tv[2 c + 1] = dL/dp_c of
+// this image for t = 1 and t = 0 (dloss applied), on the pixels whose label is not the loss's ignore_index.
 template <int KIND>
 __device__ __forceinline__ void sl_pixel_bwd(const float* lg, int C, long long tg, const SlCfg& q, float k_t, float k_p,
-                                             float* dl) {
-    if constexpr (KIND == SL_DICE_SIGMOID) {
+                                             const float* tv, float* dl) {
+    if constexpr (KIND == SL_FOCAL) {
+        const float k = tg == q.ignore_index ? 0.f : k_t;
+        for (int c = 0; c < C; ++c) dl[c] = sl_focal_bwd(lg[c], c == tg, c, q, k);
+    } else if constexpr (KIND == SL_TVERSKY) {
+        if (tg == q.ignore_class) {
+            for (int c = 0; c < C; ++c) dl[c] = 0.f;
+            return;
+        }
+        float mx = lg[0];
+        for (int c = 1; c < C; ++c) mx = fmaxf(mx, lg[c]);
+        float se = 0.f;
+        for (int c = 0; c < C; ++c) se += __expf(lg[c] - mx);
+        const float inv = 1.f / se;
+        const int tc = tg < 0 ? 0 : (tg >= C ? C - 1 : (int)tg);
+        float dot = 0.f;
+        for (int c = 0; c < C; ++c) dot += tv[2 * c + (c == tc ? 0 : 1)] * (__expf(lg[c] - mx) * inv);
+        for (int c = 0; c < C; ++c) dl[c] = __expf(lg[c] - mx) * inv * (tv[2 * c + (c == tc ? 0 : 1)] - dot);
+    } else if constexpr (KIND == SL_DICE_SIGMOID) {
         const int tc = tg < 0 ? 0 : (tg >= C ? -1 : (int)tg);
         for (int c = 0; c < C; ++c) {
             const float p = 1.f / (1.f + __expf(-lg[c]));
@@ -303,7 +365,7 @@ __global__ void __launch_bounds__(256) sl_finish_kernel(int kind, float* work, i
             const unsigned U0 = s_u[0][0] + s_u[1][0] + s_u[2][0] + s_u[3][0];
             cnt1 += s_u[0][1] + s_u[1][1] + s_u[2][1] + s_u[3][1];
             cnt2 += s_u[0][2] + s_u[1][2] + s_u[2][2] + s_u[3][2];
-            if (kind == SL_CE) {
+            if (kind == SL_CE || kind == SL_FOCAL) {
                 tot0 += F0;
                 tot1 += F1;
                 cnt0 += U0;
@@ -333,6 +395,10 @@ __global__ void __launch_bounds__(256) sl_finish_kernel(int kind, float* work, i
         out[0] = cnt0 == 0u ? 0.f : q.loss_weight * (tot0 / div);
         out[2] = div;
         out[3] = (float)cnt0;
+    } else if (kind == SL_FOCAL) {
+        out[0] = q.loss_weight * (tot0 / q.div);
+        out[2] = 0.f;
+        out[3] = 0.f;
     } else {
         out[0] = q.loss_weight * (q.reduction == 0 ? loss_sum / (float)N : loss_sum);
         out[2] = 0.f;
@@ -348,6 +414,11 @@ __device__ __forceinline__ void sl_bwd_coef(const SlCfg& q, const float* work, c
     if constexpr (KIND == SL_CE) {
         k_t = out[3] > 0.f ? g / out[2] : 0.f;
         k_p = 0.f;
+    } else if constexpr (KIND == SL_FOCAL) {
+        k_t = g / q.div;
+        k_p = 0.f;
+    } else if constexpr (KIND == SL_TVERSKY) {
+        k_t = k_p = 0.f;          // (its coefficients are per class: sl_tv_coef)
     } else {
         const float sc = q.reduction == 0 ? g / (float)N : g;
         const float a = work[4 * n], b = work[4 * n + 1], c = work[4 * n + 2];
@@ -363,6 +434,13 @@ __device__ __forceinline__ void sl_bwd_coef(const SlCfg& q, const float* work, c
     }
 }
 
+// Tversky: the 2 C backward coefficients of image n from hdr, times dloss, into LDS (C <= SL_TV_MAX_C)
+__device__ __forceinline__ void sl_tv_coef(float* s_tv, const float* work, const float* dloss, int n, int C) {
+    if ((int)threadIdx.x < 2 * C)
+        s_tv[threadIdx.x] = dloss[0] * work[((long)n * C + (threadIdx.x >> 1)) * 5 + 3 + (threadIdx.x & 1)];
+    __syncthreads();
+}
+
 template <int KIND>
 __global__ void __launch_bounds__(256) sl_bwd_kernel(const float* logits, const long long* target, long HW, int C,
                                                      const SlCfg q, const float* work, const float* out,
@@ -370,6 +448,12 @@ __global__ void __launch_bounds__(256) sl_bwd_kernel(const float* logits, const 
     const int n = blockIdx.y;
     float k_t, k_p;
     sl_bwd_coef<KIND>(q, work, out, dloss, n, N, k_t, k_p);
+    const float* tv = nullptr;
+    if constexpr (KIND == SL_TVERSKY) {
+        __shared__ float s_tv[2 * SL_TV_MAX_C];
+        sl_tv_coef(s_tv, work, dloss, n, C);
+        tv = s_tv;
+    }
     const float* lgn = logits + (long)n * HW * C;
     float* dn = dlogits + (long)n * HW * C;
     const long long* tn = target + (long)n * HW;
@@ -379,10 +463,10 @@ __global__ void __launch_bounds__(256) sl_bwd_kernel(const float* logits, const 
             const float2 v = *reinterpret_cast<const float2*>(lgn + p * 2);
             const float l2[2] = {v.x, v.y};
             float d2[2];
-            sl_pixel_bwd<KIND>(l2, 2, tn[p], q, k_t, k_p, d2);
+            sl_pixel_bwd<KIND>(l2, 2, tn[p], q, k_t, k_p, tv, d2);
             *reinterpret_cast<float2*>(dn + p * 2) = make_float2(d2[0], d2[1]);
         } else {
-            sl_pixel_bwd<KIND>(lgn + p * C, C, tn[p], q, k_t, k_p, dn + p * C);
+            sl_pixel_bwd<KIND>(lgn + p * C, C, tn[p], q, k_t, k_p, tv, dn + p * C);
         }
     }
 }
@@ -402,6 +486,12 @@ __global__ void __launch_bounds__(512) sl_up_bwd_kernel(const float* src, int N,
     const int i0 = bi * TH, j0 = bj * TW;
     float k_t, k_p;
     sl_bwd_coef<KIND>(q, work, out, dloss, n, N, k_t, k_p);
+    const float* tv = nullptr;
+    if constexpr (KIND == SL_TVERSKY) {
+        __shared__ float s_tv[4];
+        sl_tv_coef(s_tv, work, dloss, n, 2);
+        tv = s_tv;
+    }
     const float* sn = src + (long)n * Hs * Ws * 2;
     const long long* tn = target + (long)n * H * W;
     for (int k = threadIdx.x; k < CHH * CHW; k += 512) {
@@ -411,7 +501,7 @@ __global__ void __launch_bounds__(512) sl_up_bwd_kernel(const float* src, int N,
             const float2 v = sl_up(sn, Ws, lerp_coord(y, Hs, H), lerp_coord(x, Ws, W));
             const float l2[2] = {v.x, v.y};
             float d2[2];
-            sl_pixel_bwd<KIND>(l2, 2, tn[(long)y * W + x], q, k_t, k_p, d2);
+            sl_pixel_bwd<KIND>(l2, 2, tn[(long)y * W + x], q, k_t, k_p, tv, d2);
             g = make_float2(d2[0], d2[1]);
         }
         s_g[k] = g;
@@ -448,26 +538,236 @@ __global__ void __launch_bounds__(512) sl_up_bwd_kernel(const float* src, int N,
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Tversky forward: classes c0 .. c0 + CB - 1 of one pixel into the thread's 3 x CB accumulators (CB a constant and the
+// loops over it unrolled: registers, no scratch).  first: this pass also counts the accuracy.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int TV_HDR = 5;
+long long tversky_work_floats(long long N, int C) {
+    return TV_HDR * N * C + (N > SL_GRID ? N : (long long)SL_GRID) * (2 + 3LL * C);
+}
+
+template <int CB>
+struct TvAcc {
+    float tp[CB], fp[CB], fn[CB];
+    unsigned u1, u2;
+};
+
+template <int CB>
+__device__ __forceinline__ void tv_pixel_fwd(const float* lg, int C, int c0, long long tg, const SlCfg& q, TvAcc<CB>& a) {
+    float mx = lg[0];
+    int am = 0;
+    for (int c = 1; c < C; ++c)
+        if (lg[c] > mx) { mx = lg[c]; am = c; }
+    if (c0 == 0 && tg != q.ignore_index) {
+        ++a.u1;
+        if (am == tg) ++a.u2;
+    }
+    if (tg == q.ignore_class) return;
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += __expf(lg[c] - mx);
+    const float inv = 1.f / se;
+    const int tc = tg < 0 ? 0 : (tg >= C ? C - 1 : (int)tg);
+#pragma unroll
+    for (int k = 0; k < CB; ++k) {
+        const int c = c0 + k;
+        if (c < C) {
+            const float p = __expf(lg[c] - mx) * inv;
+            a.tp[k] += c == tc ? p : 0.f;
+            a.fn[k] += c == tc ? 1.f - p : 0.f;
+            a.fp[k] += c == tc ? 0.f : p;
+        }
+    }
+}
+
+template <int CB>
+__device__ __forceinline__ void tv_acc_clear(TvAcc<CB>& a) {
+#pragma unroll
+    for (int k = 0; k < CB; ++k) a.tp[k] = a.fp[k] = a.fn[k] = 0.f;
+    a.u1 = a.u2 = 0u;
+}
+
+// the workgroup's sums of classes c0 .. -> part[slot][c][3] (wave sums, then the four waves in a fixed order); with
+// c0 == 0 also its two counts -> cnt[slot][2].  Ends in a barrier: s_f may be reused at once.
+template <int CB>
+__device__ __forceinline__ void tv_block_write(const TvAcc<CB>& a, float (*s_f)[3 * CB], unsigned (*s_u)[2], int C, int c0,
+                                               float* cnt, float* part) {
+    const int wid = threadIdx.x >> 6;
+    const bool l0 = lane_id() == 0;
+#pragma unroll
+    for (int k = 0; k < CB; ++k) {
+        const float tp = wave_sum(a.tp[k]), fp = wave_sum(a.fp[k]), fn = wave_sum(a.fn[k]);
+        if (l0) {
+            s_f[wid][3 * k] = tp;
+            s_f[wid][3 * k + 1] = fp;
+            s_f[wid][3 * k + 2] = fn;
+        }
+    }
+    if (c0 == 0) {
+        const unsigned u1 = sl_wave_sum_u(a.u1), u2 = sl_wave_sum_u(a.u2);
+        if (l0) { s_u[wid][0] = u1; s_u[wid][1] = u2; }
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < 3 * CB && c0 + t / 3 < C) part[3 * c0 + t] = (s_f[0][t] + s_f[1][t]) + (s_f[2][t] + s_f[3][t]);
+    if (c0 == 0 && t < 2) cnt[t] = __uint_as_float(s_u[0][t] + s_u[1][t] + s_u[2][t] + s_u[3][t]);
+    __syncthreads();
+}
+
+// generic: grid (G, N), one pixel per thread and step, ceil(C / CB) passes over the image's pixels
+template <int CB>
+__global__ void __launch_bounds__(256) tv_fwd_kernel(const float* logits, const long long* target, long HW, int C,
+                                                     const SlCfg q, float* work, int N) {
+    __shared__ float s_f[4][3 * CB];
+    __shared__ unsigned s_u[4][2];
+    const int n = blockIdx.y;
+    const long slot = (long)n * gridDim.x + blockIdx.x, slots = (long)N * gridDim.x;
+    float* cnt = work + (long)TV_HDR * N * C + 2 * slot;
+    float* part = work + (long)TV_HDR * N * C + 2 * slots + slot * 3 * C;
+    const float* lgn = logits + (long)n * HW * C;
+    const long long* tn = target + (long)n * HW;
+    const long stride = (long)gridDim.x * 256;
+    for (int c0 = 0; c0 < C; c0 += CB) {
+        TvAcc<CB> a;
+        tv_acc_clear(a);
+        for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < HW; p += stride) {
+            if constexpr (CB == 2) {          // (two classes)
+                const float2 v = *reinterpret_cast<const float2*>(lgn + p * 2);
+                const float l2[2] = {v.x, v.y};
+                tv_pixel_fwd<CB>(l2, 2, 0, tn[p], q, a);
+            } else {
+                tv_pixel_fwd<CB>(lgn + p * C, C, c0, tn[p], q, a);
+            }
+        }
+        tv_block_write<CB>(a, s_f, s_u, C, c0, cnt, part);
+    }
+}
+
+// resize-folded (two classes): the walk of sl_up_fwd_kernel
+__global__ void __launch_bounds__(256) tv_up_fwd_kernel(const float* src, int Hs, int Ws, const long long* target,
+                                                        const SlCfg q, float* work, int N) {
+    __shared__ float s_f[4][6];
+    __shared__ unsigned s_u[4][2];
+    const int n = blockIdx.y, H = 2 * Hs, W = 2 * Ws;
+    const long slot = (long)n * gridDim.x + blockIdx.x, slots = (long)N * gridDim.x;
+    const float* sn = src + (long)n * Hs * Ws * 2;
+    const long long* tn = target + (long)n * H * W;
+    const int nq = (W + 3) / 4;
+    TvAcc<2> a;
+    tv_acc_clear(a);
+    for (int y = blockIdx.x; y < H; y += gridDim.x) {
+        const Lerp ly = lerp_coord(y, Hs, H);
+        for (int qx = threadIdx.x; qx < nq; qx += 256) {
+            float2 lg[4];
+            long long tg[4];
+            const int cnt = sl_quad(sn, tn + (long)y * W, Ws, W, ly, qx, lg, tg);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (k < cnt) {
+                    const float l2[2] = {lg[k].x, lg[k].y};
+                    tv_pixel_fwd<2>(l2, 2, 0, tg[k], q, a);
+                }
+            }
+        }
+    }
+    tv_block_write<2>(a, s_f, s_u, 2, 0, work + (long)TV_HDR * N * 2 + 2 * slot,
+                      work + (long)TV_HDR * N * 2 + 2 * slots + slot * 6);
+}
+
+// finish: ONE workgroup.  Every (image, class, sum) series of G partials is added by one wave in a fixed order; then a
+// thread per (image, class) forms the term and the backward's two coefficients, and the terms are added in a fixed order.
+__global__ void __launch_bounds__(256) tv_finish_kernel(float* work, int N, int C, int G, const SlCfg q, float* out) {
+    __shared__ float s_f[4];
+    __shared__ unsigned s_u[4][2];
+    const float* cnt = work + (long)TV_HDR * N * C;
+    const float* part = cnt + 2L * N * G;
+    const int wid = threadIdx.x >> 6, lane = lane_id();
+    const long series = 3L * N * C;
+    for (long e = wid; e < series; e += 4) {
+        const long n = e / (3 * C);
+        const int r = (int)(e % (3 * C));          // = 3 c + j
+        float a = 0.f;
+        for (int b = lane; b < G; b += 64) a += part[(n * G + b) * 3 * C + r];
+        a = wave_sum(a);
+        if (lane == 0) work[(n * C + r / 3) * TV_HDR + r % 3] = a;
+    }
+    unsigned u1 = 0u, u2 = 0u;          // < 2^31: the entry points require N*HW < 2^31
+    for (long i = threadIdx.x; i < (long)N * G; i += 256) {
+        u1 += __float_as_uint(cnt[2 * i]);
+        u2 += __float_as_uint(cnt[2 * i + 1]);
+    }
+    u1 = sl_wave_sum_u(u1);
+    u2 = sl_wave_sum_u(u2);
+    if (lane == 0) { s_u[wid][0] = u1; s_u[wid][1] = u2; }
+    __syncthreads();          // (the sums in hdr are the workgroup's own writes: visible after the barrier)
+    float acc = 0.f;
+    for (long e = threadIdx.x; e < (long)N * C; e += 256) {
+        const int i = (int)(e % C);
+        float* h = work + e * TV_HDR;
+        const float TP = h[0], FP = h[1], FN = h[2];
+        const float num = TP + q.eps, D = TP + q.alpha * FP + q.beta * FN + q.eps;
+        const float w = i == q.ignore_class ? 0.f : (q.cw ? q.cw[i] : 1.f);
+        acc += w * (1.f - num / D);
+        const float K = w * q.loss_weight / ((float)C * (float)N), iD2 = 1.f / (D * D);
+        h[3] = K * (-(D - num) - q.beta * num) * iD2;          // t = 1: d/dTP - d/dFN
+        h[4] = K * (q.alpha * num) * iD2;                      // t = 0: d/dFP
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) s_f[wid] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const unsigned c1 = s_u[0][0] + s_u[1][0] + s_u[2][0] + s_u[3][0], c2 = s_u[0][1] + s_u[1][1] + s_u[2][1] + s_u[3][1];
+    out[0] = q.loss_weight * (((s_f[0] + s_f[1]) + (s_f[2] + s_f[3])) / (float)N) / (float)C;
+    out[1] = ((float)c2 + SL_F32_EPS) * (100.0f / ((float)c1 + SL_F32_EPS));
+    out[2] = 0.f;
+    out[3] = 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 #define SL_DISPATCH(kind, LAUNCH)                                \
     do {                                                         \
         if ((kind) == SL_CE) { LAUNCH(SL_CE); }                  \
         else if ((kind) == SL_DICE_SIGMOID) { LAUNCH(SL_DICE_SIGMOID); } \
+        else if ((kind) == SL_FOCAL) { LAUNCH(SL_FOCAL); }       \
         else { LAUNCH(SL_DICE_SOFTMAX); }                        \
+    } while (0)
+// (Tversky shares the backward kernels only)
+#define SL_DISPATCH_BWD(kind, LAUNCH)                            \
+    do {                                                         \
+        if ((kind) == SL_TVERSKY) { LAUNCH(SL_TVERSKY); }        \
+        else SL_DISPATCH(kind, LAUNCH);                          \
     } while (0)
 
 static bool sl_cfg_ok(int kind, const SlCfg& q) {
-    if (kind < SL_CE || kind > SL_DICE_SOFTMAX) return false;
+    if (kind < SL_CE || kind > SL_TVERSKY) return false;
     if (q.reduction != 0 && q.reduction != 1) return false;
+    if (kind == SL_FOCAL) return q.gamma >= 0.f;
     return kind == SL_CE || q.eps >= 0.f;
 }
+// Focal: the divisor of the sum, from the host's sizes
+static SlCfg sl_with_div(int kind, SlCfg q, long long elems) {
+    q.div = kind == SL_FOCAL && q.reduction == 0 ? (float)elems : 1.f;
+    return q;
+}
 
-int seg_loss_fwd_impl(int kind, const float* logits, const long long* target, int N, long long HW, int C, const SlCfg& q,
+int seg_loss_fwd_impl(int kind, const float* logits, const long long* target, int N, long long HW, int C, const SlCfg& q0,
                       float* work, float* out, hipStream_t s) {
-    LEDN_REQUIRE(logits && target && work && out && N > 0 && N <= 65535 && HW > 0 && C > 1 && sl_cfg_ok(kind, q));
+    LEDN_REQUIRE(logits && target && work && out && N > 0 && N <= 65535 && HW > 0 && C > 1 && sl_cfg_ok(kind, q0));
     LEDN_REQUIRE((long long)N * HW < (1LL << 31) && (long long)N * HW * C < (1LL << 40));
     LEDN_REQUIRE(C != 2 || ((uintptr_t)logits & 7) == 0);
+    const SlCfg q = sl_with_div(kind, q0, (long long)N * HW * C);
+    if (kind == SL_TVERSKY) {
+        LEDN_REQUIRE(C <= SL_TV_MAX_C);
+        const int G = sl_grid(N, cdiv(HW, 256));
+        const dim3 grid((unsigned)G, (unsigned)N);
+        if (C == 2)
+            LEDN_LAUNCH(tv_fwd_kernel<2>, grid, dim3(256), 0, s, logits, target, (long)HW, C, q, work, N);
+        else
+            LEDN_LAUNCH(tv_fwd_kernel<8>, grid, dim3(256), 0, s, logits, target, (long)HW, C, q, work, N);
+        LEDN_LAUNCH(tv_finish_kernel, dim3(1), dim3(256), 0, s, work, N, C, G, q, out);
+        return check_launch();
+    }
     const int G = sl_grid(N, cdiv(HW, 256));
     const dim3 grid((unsigned)G, (unsigned)N);
 #define SL_L(K) LEDN_LAUNCH(sl_fwd_kernel<K>, grid, dim3(256), 0, s, logits, target, (long)HW, C, q, work, N)
@@ -477,10 +777,12 @@ int seg_loss_fwd_impl(int kind, const float* logits, const long long* target, in
     return check_launch();
 }
 
-int seg_loss_bwd_impl(int kind, const float* logits, const long long* target, int N, long long HW, int C, const SlCfg& q,
+int seg_loss_bwd_impl(int kind, const float* logits, const long long* target, int N, long long HW, int C, const SlCfg& q0,
                       const float* work, const float* out, const float* dloss, float* dlogits, hipStream_t s) {
     LEDN_REQUIRE(logits && target && work && out && dloss && dlogits && N > 0 && N <= 65535 && HW > 0 && C > 1);
-    LEDN_REQUIRE(sl_cfg_ok(kind, q) && (long long)N * HW < (1LL << 31) && (long long)N * HW * C < (1LL << 40));
+    LEDN_REQUIRE(sl_cfg_ok(kind, q0) && (long long)N * HW < (1LL << 31) && (long long)N * HW * C < (1LL << 40));
+    LEDN_REQUIRE(kind != SL_TVERSKY || C <= SL_TV_MAX_C);
+    const SlCfg q = sl_with_div(kind, q0, (long long)N * HW * C);
     LEDN_REQUIRE(C != 2 || (((uintptr_t)logits | (uintptr_t)dlogits) & 7) == 0);
     long g = 4 * SL_GRID / N;
     if (g < 1) g = 1;
@@ -488,7 +790,7 @@ int seg_loss_bwd_impl(int kind, const float* logits, const long long* target, in
     const dim3 grid((unsigned)g, (unsigned)N);
 #define SL_L(K) \
     LEDN_LAUNCH(sl_bwd_kernel<K>, grid, dim3(256), 0, s, logits, target, (long)HW, C, q, work, out, dloss, dlogits, N)
-    SL_DISPATCH(kind, SL_L);
+    SL_DISPATCH_BWD(kind, SL_L);
 #undef SL_L
     return check_launch();
 }
@@ -501,10 +803,16 @@ static bool sl_up_ok(const float* src, const long long* target, int N, int Hs, i
 }
 
 int seg_loss_up_fwd_impl(int kind, const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
-                         const SlCfg& q, float* work, float* out, hipStream_t s) {
-    LEDN_REQUIRE(sl_up_ok(src, target, N, Hs, Ws, H, W) && work && out && sl_cfg_ok(kind, q));
+                         const SlCfg& q0, float* work, float* out, hipStream_t s) {
+    LEDN_REQUIRE(sl_up_ok(src, target, N, Hs, Ws, H, W) && work && out && sl_cfg_ok(kind, q0));
+    const SlCfg q = sl_with_div(kind, q0, (long long)N * H * W * 2);
     const int G = sl_grid(N, H);
     const dim3 grid((unsigned)G, (unsigned)N);
+    if (kind == SL_TVERSKY) {
+        LEDN_LAUNCH(tv_up_fwd_kernel, grid, dim3(256), 0, s, src, Hs, Ws, target, q, work, N);
+        LEDN_LAUNCH(tv_finish_kernel, dim3(1), dim3(256), 0, s, work, N, 2, G, q, out);
+        return check_launch();
+    }
 #define SL_L(K) LEDN_LAUNCH(sl_up_fwd_kernel<K>, grid, dim3(256), 0, s, src, Hs, Ws, target, q, work, N)
     SL_DISPATCH(kind, SL_L);
 #undef SL_L
@@ -513,15 +821,16 @@ int seg_loss_up_fwd_impl(int kind, const float* src, int N, int Hs, int Ws, int 
 }
 
 int seg_loss_up_bwd_impl(int kind, const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
-                         const SlCfg& q, const float* work, const float* out, const float* dloss, float* dsrc,
+                         const SlCfg& q0, const float* work, const float* out, const float* dloss, float* dsrc,
                          hipStream_t s) {
-    LEDN_REQUIRE(sl_up_ok(src, target, N, Hs, Ws, H, W) && work && out && dloss && dsrc && sl_cfg_ok(kind, q));
+    LEDN_REQUIRE(sl_up_ok(src, target, N, Hs, Ws, H, W) && work && out && dloss && dsrc && sl_cfg_ok(kind, q0));
     LEDN_REQUIRE(((uintptr_t)dsrc & 7) == 0);
+    const SlCfg q = sl_with_div(kind, q0, (long long)N * H * W * 2);
     const long nb = (long)N * cdiv(Hs, 8) * cdiv(Ws, 64);
     LEDN_REQUIRE(nb < (1L << 31));
 #define SL_L(K) \
     LEDN_LAUNCH(sl_up_bwd_kernel<K>, dim3((unsigned)nb), dim3(512), 0, s, src, N, Hs, Ws, target, q, work, out, dloss, dsrc)
-    SL_DISPATCH(kind, SL_L);
+    SL_DISPATCH_BWD(kind, SL_L);
 #undef SL_L
     return check_launch();
 }

@@ -1,4 +1,5 @@
-"""OhemCrossEntropy, CrossEntropyLoss and DiceLoss (registered under the reference's names) and accuracy.
+"""OhemCrossEntropy, CrossEntropyLoss, DiceLoss, FocalLoss and TverskyLoss (registered under the reference's names)
+and accuracy.
 
 Mirrors mmseg/models/losses/ohem_cross_entropy_loss.py:11-94 (constructor
 arguments, ``loss_name`` property, selection semantics) and
@@ -12,6 +13,9 @@ CrossEntropyLoss (softmax form) and DiceLoss mirror losses/cross_entropy_loss.py
 constructor signatures, ``loss_name``, an empty state_dict.  Their arithmetic runs in csrc/seg_loss.hip (one streaming
 pass + a fixed-order finish, the divisor formed on the device, nothing per-pixel stored); see DESIGN.md
 "CrossEntropyLoss and DiceLoss in the head" for the layouts and the two deviations from the reference.
+
+FocalLoss (sigmoid form) and TverskyLoss mirror losses/focal_loss.py:136-337 and losses/tversky_loss.py:60-137 in the
+same way, on further kernels of csrc/seg_loss.hip; DESIGN.md "FocalLoss and TverskyLoss in the head".
 """
 import math
 
@@ -151,6 +155,115 @@ class DiceLoss(nn.Module):
         return 'dice', dict(bwd, acc_ignore_index=ignore_index), bwd
 
     def forward(self, pred, target, ignore_index=255):
+        """pred: N x C x H x W (any float layout), target: N x H x W int64."""
+        from .train import seg_loss
+        return seg_loss(self, pred, target, ignore_index)
+
+    @property
+    def loss_name(self):
+        return self._loss_name
+
+
+@MODELS.register_module()
+class FocalLoss(_ClassWeighted):
+    """losses/focal_loss.py:136-337, the sigmoid form as FocalLoss.forward's GPU branch computes it (:241-284 + the
+    arithmetic of py_sigmoid_focal_loss, :45-67).  'mean' divides by N*H*W*C: ignored pixels stay in the divisor.  A
+    label outside [0, C) that is not ``ignore_index`` has an all-zero target row (the reference gets that far only for
+    label == C)."""
+
+    def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.5, reduction='mean', class_weight=None, loss_weight=1.0,
+                 loss_name='loss_focal'):
+        super().__init__()
+        if use_sigmoid is not True:
+            raise NotImplementedError('FocalLoss: use_sigmoid=False is not supported (only the sigmoid form exists)')
+        if isinstance(class_weight, str):
+            raise TypeError(f'FocalLoss: class_weight={class_weight!r}: a file path is not supported, give the list '
+                            f'of weights')
+        if isinstance(alpha, (list, tuple)):
+            if not alpha or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in alpha):
+                raise ValueError('FocalLoss: alpha must be a float or a list of one finite number per class')
+        elif not isinstance(alpha, (int, float)) or isinstance(alpha, bool) or not math.isfinite(alpha):
+            raise TypeError(f'FocalLoss: alpha={alpha!r} must be a float or a list of floats')
+        if not isinstance(gamma, (int, float)) or isinstance(gamma, bool) or not gamma >= 0:
+            raise ValueError(f'FocalLoss: gamma={gamma!r} must be a number >= 0')
+        self.use_sigmoid = True
+        self.gamma = gamma
+        self.alpha = alpha
+        self.reduction = _checked_reduction('FocalLoss', reduction)
+        self.loss_weight = loss_weight
+        self._set_class_weight(class_weight)
+        # (a list's device copy, like class_weight's: not persistent, the state_dict stays empty)
+        self.register_buffer('_alpha', torch.tensor([float(v) for v in alpha], dtype=torch.float32)
+                             if isinstance(alpha, (list, tuple)) else None, persistent=False)
+        self._loss_name = loss_name
+
+    def alpha_on(self, logits):
+        """alpha as the kernels take it: the float, or the [C] f32 buffer, checked against channels-last `logits`"""
+        a = self._alpha
+        if a is None:
+            return float(self.alpha)
+        if a.numel() != logits.shape[-1]:
+            raise ValueError(f'{self.loss_name}: alpha has {a.numel()} entries but the logits have '
+                             f'{logits.shape[-1]} classes')
+        if a.device != logits.device:
+            raise RuntimeError(f'{self.loss_name}: alpha is on {a.device}, the logits on {logits.device} (move the '
+                               f'module with .to(device))')
+        return a
+
+    def kernel_args(self, logits, ignore_index):
+        """(family, keyword arguments of ops_train.focal_loss*_fwd, of *_bwd) for channels-last `logits`"""
+        kw = dict(loss_weight=self.loss_weight, gamma=self.gamma, alpha=self.alpha_on(logits), ignore_index=ignore_index,
+                  class_weight=self.class_weight_on(logits), reduction=self.reduction)
+        return 'focal', kw, kw
+
+    def forward(self, pred, target, ignore_index=255):
+        """pred: N x C x H x W (any float layout), target: N x H x W int64."""
+        from .train import seg_loss
+        return seg_loss(self, pred, target, ignore_index)
+
+    @property
+    def loss_name(self):
+        return self._loss_name
+
+
+@MODELS.register_module()
+class TverskyLoss(_ClassWeighted):
+    """losses/tversky_loss.py:60-137.  ``ignore_index`` is the loss's own: pixels LABELLED so are masked out of the
+    sums and the class of that index is left out of the loss (which is still divided by C); the ``ignore_index`` of the
+    call only selects the pixels of the reported accuracy, as the reference's forward ignores it.  2 to 32 classes.
+    ``smooth=0`` is accepted as the reference accepts it: an image without a valid pixel then gives 0 / 0 = NaN."""
+
+    def __init__(self, smooth=1, class_weight=None, loss_weight=1.0, ignore_index=255, alpha=0.3, beta=0.7,
+                 loss_name='loss_tversky'):
+        super().__init__()
+        if isinstance(class_weight, str):
+            raise TypeError(f'TverskyLoss: class_weight={class_weight!r}: a file path is not supported, give the list '
+                            f'of weights')
+        if not alpha + beta == 1.0:
+            raise ValueError(f'TverskyLoss: alpha + beta must be 1.0 (alpha={alpha!r}, beta={beta!r})')
+        if not smooth >= 0:
+            raise ValueError(f'TverskyLoss: smooth={smooth!r} must be >= 0')
+        self.smooth = smooth
+        self._set_class_weight(class_weight)
+        self.loss_weight = loss_weight
+        self.ignore_index = ignore_index
+        self.alpha = alpha
+        self.beta = beta
+        self._loss_name = loss_name
+
+    def kernel_args(self, logits, ignore_index):
+        """(family, keyword arguments of ops_train.tversky_loss*_fwd, of *_bwd); `ignore_index`: the label the accuracy
+        leaves out"""
+        from .ops_train import TVERSKY_MAX_CLASSES
+        if logits.shape[-1] > TVERSKY_MAX_CLASSES:
+            raise ValueError(f'{self.loss_name}: {logits.shape[-1]} classes; TverskyLoss takes at most '
+                             f'{TVERSKY_MAX_CLASSES}')
+        fwd = dict(loss_weight=self.loss_weight, alpha=self.alpha, beta=self.beta, smooth=self.smooth,
+                   ignore_index=self.ignore_index, class_weight=self.class_weight_on(logits),
+                   acc_ignore_index=ignore_index)
+        return 'tversky', fwd, dict(ignore_index=self.ignore_index)
+
+    def forward(self, pred, target, ignore_index=255, **kwargs):
         """pred: N x C x H x W (any float layout), target: N x H x W int64."""
         from .train import seg_loss
         return seg_loss(self, pred, target, ignore_index)

@@ -765,6 +765,156 @@ def dice_loss_up_bwd(src, target, work, out, dloss, loss_weight=1.0, use_sigmoid
                           reduction, eps, loss_weight)
 
 
+# --------------------------------------------------------------------------- #
+# FocalLoss (sigmoid form) / TverskyLoss (csrc/seg_loss.hip): the same two families
+# --------------------------------------------------------------------------- #
+TVERSKY_MAX_CLASSES = 32
+
+
+def _focal_cfg(who, logits, class_weight, alpha, gamma, ignore_index, reduction, loss_weight):
+    Cc = logits.shape[-1]
+    cw = _class_weight(class_weight, logits, Cc, who)
+    if torch.is_tensor(alpha):
+        try:
+            av, a = _class_weight(alpha, logits, Cc, who), 0.5
+        except LednError as e:
+            raise LednError(str(e).replace('class_weight', 'alpha')) from None
+    else:
+        av, a = None, float(alpha)
+    if not float(gamma) >= 0:
+        raise LednError(f'{who}: gamma={gamma!r} must be >= 0')
+    return cw, av, (_p(cw), _p(av), a, float(gamma), int(ignore_index), _REDUCTIONS[reduction], float(loss_weight))
+
+
+def _focal_loss_fwd(who, up, logits, target, class_weight, alpha, gamma, ignore_index, reduction, loss_weight):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, up, reduction)
+    cw, av, cfg = _focal_cfg(who, logits, class_weight, alpha, gamma, ignore_index, reduction, loss_weight)
+    work, out = _seg_loss_bufs(lib, N, logits)
+    _check(lib, logits, target, work, out)
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{logits.shape[-1]}', _nb(logits, target), 30 * P * logits.shape[-1],
+                                           'sl_up_fwd_kernel' if up else 'sl_fwd_kernel')
+    if up:
+        _run(lib, 'ledn_focal_loss_up_fwd', logits, _p(logits), *shape, _p(target), *cfg, _p(work), _p(out), work=timing)
+    else:
+        _run(lib, 'ledn_focal_loss_fwd', logits, _p(logits), _p(target), *shape, *cfg, _p(work), _p(out), work=timing)
+    return out, work
+
+
+def _focal_loss_bwd(who, up, logits, target, work, out, dloss, class_weight, alpha, gamma, ignore_index, reduction,
+                    loss_weight):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, up, reduction)
+    cw, av, cfg = _focal_cfg(who, logits, class_weight, alpha, gamma, ignore_index, reduction, loss_weight)
+    dl = torch.empty_like(logits)
+    dloss = dloss.reshape(1).to(torch.float32).contiguous()
+    _check(lib, logits, target, work, out, dloss, dl)
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{logits.shape[-1]}', _nb(logits, target, dl), 40 * P * logits.shape[-1],
+                                           'sl_up_bwd_kernel' if up else 'sl_bwd_kernel')
+    if up:
+        _run(lib, 'ledn_focal_loss_up_bwd', logits, _p(logits), *shape, _p(target), *cfg, _p(work), _p(out), _p(dloss), _p(dl),
+             work=timing)
+    else:
+        _run(lib, 'ledn_focal_loss_bwd', logits, _p(logits), _p(target), *shape, *cfg, _p(work), _p(out), _p(dloss), _p(dl),
+             work=timing)
+    return dl
+
+
+def focal_loss_fwd(logits, target, loss_weight=1.0, gamma=2.0, alpha=0.5, ignore_index=255, class_weight=None,
+                   reduction='mean'):
+    """FocalLoss (sigmoid form): logits [N,H,W,C] f32, target [N,H,W] int64 -> (out[4] = loss, acc, 0, 0 ; work).
+    alpha: a float or a [C] f32 vector on the device; class_weight: None or such a vector.  'mean' divides by N*H*W*C
+    (ignored pixels stay in the divisor)."""
+    return _focal_loss_fwd('focal_loss', False, logits, target, class_weight, alpha, gamma, ignore_index, reduction, loss_weight)
+
+
+def focal_loss_bwd(logits, target, work, out, dloss, loss_weight=1.0, gamma=2.0, alpha=0.5, ignore_index=255,
+                   class_weight=None, reduction='mean'):
+    return _focal_loss_bwd('focal_loss_bwd', False, logits, target, work, out, dloss, class_weight, alpha, gamma, ignore_index,
+                           reduction, loss_weight)
+
+
+def focal_loss_up_fwd(src, target, loss_weight=1.0, gamma=2.0, alpha=0.5, ignore_index=255, class_weight=None,
+                      reduction='mean'):
+    """FocalLoss on bilinear(src -> target's H x W = 2 Hs x 2 Ws) without materialising the resized logits."""
+    return _focal_loss_fwd('focal_loss_up', True, src, target, class_weight, alpha, gamma, ignore_index, reduction, loss_weight)
+
+
+def focal_loss_up_bwd(src, target, work, out, dloss, loss_weight=1.0, gamma=2.0, alpha=0.5, ignore_index=255,
+                      class_weight=None, reduction='mean'):
+    return _focal_loss_bwd('focal_loss_up_bwd', True, src, target, work, out, dloss, class_weight, alpha, gamma, ignore_index,
+                           reduction, loss_weight)
+
+
+def _tversky_args(who, logits, target, up):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, up, 'mean')
+    if logits.shape[-1] > TVERSKY_MAX_CLASSES:
+        raise LednError(f'{who}: {logits.shape[-1]} classes; the Tversky kernels take at most {TVERSKY_MAX_CLASSES}')
+    return lib, N, shape, P
+
+
+def _tversky_loss_fwd(who, up, logits, target, class_weight, alpha, beta, smooth, ignore_index, acc_ignore_index,
+                      loss_weight):
+    lib, N, shape, P = _tversky_args(who, logits, target, up)
+    Cc = logits.shape[-1]
+    cw = _class_weight(class_weight, logits, Cc, who)
+    if not smooth >= 0:
+        raise LednError(f'{who}: smooth={smooth!r} must be >= 0')
+    work = torch.empty(lib.cdll.ledn_tversky_work_floats(N, Cc), dtype=torch.float32, device=logits.device)
+    out = torch.empty(4, dtype=torch.float32, device=logits.device)
+    _check(lib, logits, target, work, out)
+    cfg = (_p(cw), float(alpha), float(beta), float(smooth), _dice_class(ignore_index), int(acc_ignore_index),
+           float(loss_weight))
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{Cc}', _nb(logits, target), 20 * P * Cc,
+                                           'tv_up_fwd_kernel' if up else 'tv_fwd_kernel')
+    if up:
+        _run(lib, 'ledn_tversky_loss_up_fwd', logits, _p(logits), *shape, _p(target), *cfg, _p(work), _p(out), work=timing)
+    else:
+        _run(lib, 'ledn_tversky_loss_fwd', logits, _p(logits), _p(target), *shape, *cfg, _p(work), _p(out), work=timing)
+    return out, work
+
+
+def _tversky_loss_bwd(who, up, logits, target, work, out, dloss, ignore_index):
+    lib, N, shape, P = _tversky_args(who, logits, target, up)
+    Cc = logits.shape[-1]
+    if work.numel() < lib.cdll.ledn_tversky_work_floats(N, Cc):
+        raise LednError(f'{who}: work is not the forward\'s (too small for {N} images of {Cc} classes)')
+    dl = torch.empty_like(logits)
+    dloss = dloss.reshape(1).to(torch.float32).contiguous()
+    _check(lib, logits, target, work, out, dloss, dl)
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{Cc}', _nb(logits, target, dl), 30 * P * Cc,
+                                           'sl_up_bwd_kernel' if up else 'sl_bwd_kernel')
+    if up:
+        _run(lib, 'ledn_tversky_loss_up_bwd', logits, _p(logits), *shape, _p(target), _dice_class(ignore_index), _p(work),
+             _p(out), _p(dloss), _p(dl), work=timing)
+    else:
+        _run(lib, 'ledn_tversky_loss_bwd', logits, _p(logits), _p(target), *shape, _dice_class(ignore_index), _p(work),
+             _p(out), _p(dloss), _p(dl), work=timing)
+    return dl
+
+
+def tversky_loss_fwd(logits, target, loss_weight=1.0, alpha=0.3, beta=0.7, smooth=1.0, ignore_index=255, class_weight=None,
+                     acc_ignore_index=255):
+    """TverskyLoss: logits [N,H,W,C] f32 (2 <= C <= 32), target [N,H,W] int64 -> (out[4] = loss, acc, 0, 0 ; work, whose
+    first 5 N C floats are per (image, class) TP, FP, FN and the backward's two coefficients).  ignore_index: the
+    loss's own (the masked label and the skipped class); acc_ignore_index: the label left out of the accuracy."""
+    return _tversky_loss_fwd('tversky_loss', False, logits, target, class_weight, alpha, beta, smooth, ignore_index,
+                             acc_ignore_index, loss_weight)
+
+
+def tversky_loss_bwd(logits, target, work, out, dloss, ignore_index=255):
+    return _tversky_loss_bwd('tversky_loss_bwd', False, logits, target, work, out, dloss, ignore_index)
+
+
+def tversky_loss_up_fwd(src, target, loss_weight=1.0, alpha=0.3, beta=0.7, smooth=1.0, ignore_index=255, class_weight=None,
+                        acc_ignore_index=255):
+    """TverskyLoss on bilinear(src -> target's H x W = 2 Hs x 2 Ws) without materialising the resized logits."""
+    return _tversky_loss_fwd('tversky_loss_up', True, src, target, class_weight, alpha, beta, smooth, ignore_index,
+                             acc_ignore_index, loss_weight)
+
+
+def tversky_loss_up_bwd(src, target, work, out, dloss, ignore_index=255):
+    return _tversky_loss_bwd('tversky_loss_up_bwd', True, src, target, work, out, dloss, ignore_index)
+
+
 def mfaf_ctx_fwd(pooled, seqs, training, stats1=None, momentum=0.1, tails=None, sync=None, world=1):
     """The four pooled-context MLPs of Muti_AFF in one launch sequence (ledn_mfaf_ctx_fwd).
     pooled: 4 f32 [N,S,S,C] maps; seqs: 4 x (conv1, bn1, conv2) modules.  -> (z2 list [N,S,S,C] f32, saved dict)

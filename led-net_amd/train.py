@@ -1387,8 +1387,8 @@ class OhemUp2Fn(Function):
 
 
 class SegLossFn(Function):
-    """CrossEntropyLoss / DiceLoss through csrc/seg_loss.hip: on NHWC logits (up = False) or on resize(src -> label
-    size) with the exact 2x resize folded into the kernels (up = True).  -> (loss, out[4])"""
+    """CrossEntropyLoss / DiceLoss / FocalLoss / TverskyLoss through csrc/seg_loss.hip: on NHWC logits (up = False) or
+    on resize(src -> label size) with the exact 2x resize folded into the kernels (up = True).  -> (loss, out[4])"""
 
     @staticmethod
     def forward(ctx, x, target, family, up, fwd_kw, bwd_kw):
@@ -1411,7 +1411,8 @@ class SegLossFn(Function):
 
 
 def seg_loss_apply(crit, x, target, up, ignore_index):
-    """CrossEntropyLoss / DiceLoss `crit` on channels-last f32 `x` (up: x is the half-size source) -> (loss, out[4])"""
+    """CrossEntropyLoss / DiceLoss / FocalLoss / TverskyLoss `crit` on channels-last f32 `x` (up: x is the half-size
+    source) -> (loss, out[4])"""
     family, fwd_kw, bwd_kw = crit.kernel_args(x, ignore_index)
     if up and target.data_ptr() % 16:
         target = target.clone()          # (a view at an odd offset: the kernels read two labels per 16-byte load)
@@ -1419,7 +1420,7 @@ def seg_loss_apply(crit, x, target, up, ignore_index):
 
 
 def seg_loss(crit, score, target, ignore_index):
-    """CrossEntropyLoss.forward / DiceLoss.forward on NCHW(-view) logits."""
+    """The forward of CrossEntropyLoss, DiceLoss, FocalLoss and TverskyLoss on NCHW(-view) logits."""
     from .lednet import to_nhwc
     return seg_loss_apply(crit, to_nhwc(score, torch.float32), target.contiguous(), False, ignore_index)[0]
 
@@ -1446,8 +1447,8 @@ def led_head_loss_by_feat(h, seg_logits, batch_data_samples):
     fold = bool(FUSE_LOSS_RESIZE and H % 2 == 0 and W % 2 == 0 and xc.shape[-1] == 2)
     from .losses import OhemCrossEntropy
     if not (isinstance(c0, OhemCrossEntropy) and isinstance(c1, OhemCrossEntropy)):
-        # CrossEntropyLoss / DiceLoss somewhere: each entry runs on its own (csrc/seg_loss.hip for the new losses, the
-        # single-loss OHEM kernels for an OhemCrossEntropy next to one of them)
+        # a CrossEntropyLoss, DiceLoss, FocalLoss or TverskyLoss somewhere: each entry runs on its own (csrc/seg_loss.hip
+        # for those four, the single-loss OHEM kernels for an OhemCrossEntropy next to one of them)
         losses, outs = [], []
         for crit, logit in ((c0, xc), (c1, xs)):
             x = fuse_loss_half(logit, h1, h2, hw) if fold else fuse_loss(logit, h1, h2, hw)

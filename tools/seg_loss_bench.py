@@ -6,6 +6,12 @@ events, median of --repeats after --warmup), loss kernels only, on --batch x --h
   ce + dice:  ledn_ce_loss_up_fwd + ledn_dice_loss_up_fwd, then ledn_dice_loss_up_bwd + ledn_ce_loss_up_bwd
               (the launch set of the [CE, Dice] head: each loss on its own)
 
+Then each resize-folded launch on its own, FocalLoss and TverskyLoss next to the CrossEntropyLoss / DiceLoss launches
+of the same shape (the in-tree yardstick), with the ratio to each of them:
+
+  ce / dice / focal / tversky fwd:  ledn_{ce,dice,focal,tversky}_loss_up_fwd (pass + finish)
+  ce / dice / focal / tversky bwd:  ledn_{ce,dice,focal,tversky}_loss_up_bwd
+
 GB/s: the bytes a launch set must move at least (int64 labels and the half-size sources once per kernel that reads
 them, the source gradients once) over the median time.
 
@@ -95,6 +101,24 @@ def main():
             lines.append(f'  #{rep} {k:12s} {fmt(t, traffic[k])}')
         lines.append(f'  #{rep} fwd + bwd    ohem pair {res["ohem fwd"][0] + res["ohem bwd"][0]:.3f} ms   '
                      f'ce + dice {res["ce+dice fwd"][0] + res["ce+dice bwd"][0]:.3f} ms')
+    # the four families launch by launch: forward = labels + source read, backward = those + the source gradient
+    fams = {'ce': (T.ce_loss_up_fwd, T.ce_loss_up_bwd, dict(loss_weight=1.0, ignore_index=255, avg_non_ignore=True),
+                   dict(loss_weight=1.0, ignore_index=255)),
+            'dice': (T.dice_loss_up_fwd, T.dice_loss_up_bwd, dict(loss_weight=0.4), dict(loss_weight=0.4)),
+            'focal': (T.focal_loss_up_fwd, T.focal_loss_up_bwd, dict(gamma=2.0, alpha=0.5), dict(gamma=2.0, alpha=0.5)),
+            'tversky': (T.tversky_loss_up_fwd, T.tversky_loss_up_bwd, dict(alpha=0.3, beta=0.7, loss_weight=0.4), dict())}
+    saved = {k: f[0](s0, y, **f[2]) for k, f in fams.items()}
+    for rep in range(2):
+        res = {}
+        for k, (fwd, bwd, fkw, bkw) in fams.items():
+            res[k, 'fwd'] = timed(lambda: fwd(s0, y, **fkw), a.warmup, a.repeats)
+            res[k, 'bwd'] = timed(lambda: bwd(s0, y, saved[k][1], saved[k][0], one, **bkw), a.warmup, a.repeats)
+        for d, nbytes in (('fwd', lab8 + src), ('bwd', lab8 + 2 * src)):
+            for k in fams:
+                t = res[k, d]
+                ratio = '' if k in ('ce', 'dice') else \
+                    f'  x{t[0] / res["ce", d][0]:.2f} of ce, x{t[0] / res["dice", d][0]:.2f} of dice'
+                lines.append(f'  #{rep} {k + " " + d:12s} {fmt(t, nbytes)}{ratio}')
     text = '\n'.join(lines)
     print(text)
     if a.out:
