@@ -673,7 +673,10 @@ int ledn_dwconv2d_bwd_weight(const ledn_dwbwd_desc* d, void* stream);
  * Call bwd_data before bwd_weight with the SAME descriptor (dy must stay valid for both).  gsum is scratch owned by
  * the pair: on the spatial branch's shape class (bf16, stride 1, dilations 1, >= 16384 pixels) the data gradient reads
  * dy through an LDS-staged patch with prefix-summed filters and the weight gradient forms the suffix sums from dy
- * itself -- gsum is then left untouched. */
+ * itself -- gsum is then left untouched.  The same holds for pyr_bwd_data_ctx_kernel (csrc/stencil_bf16.hip), which serves
+ * every other bf16 call with LEDN_OPT_STREAM_FAST bit 1, n = 8 * 2^k <= 512, stride 1 or 2 and halos (dil at stride 1,
+ * ceil(dil / 2) at stride 2) of at most 4 whose four patches fit its LDS image (dilations [1,2,3,4] do): its dx is
+ * bit-identical to the suffix-sum + gather pair it replaces. */
 typedef struct {
     const void* x;
     const void* dy;
@@ -687,6 +690,10 @@ typedef struct {
 } ledn_pyrbwd_desc;
 int ledn_sesp_pyramid_bwd_data(const ledn_pyrbwd_desc* d, void* stream);
 int ledn_sesp_pyramid_bwd_weight(const ledn_pyrbwd_desc* d, void* stream);
+/* which kernel ledn_sesp_pyramid_bwd_data runs d on (no launch; only the shape fields and dtype are read, gsum must be
+ * non-NULL): 0 pyr_bwd_data_kernel, 1 pyr_bwd_data_bf16_kernel (both after pyr_suffix_kernel, gsum written),
+ * 2 pyr_bwd_data_tile_kernel, 3 pyr_bwd_data_ctx_kernel (both straight from dy, gsum untouched by either entry point); -1 for a descriptor the entry points reject */
+int ledn_sesp_pyramid_bwd_kernel_id(const ledn_pyrbwd_desc* d);
 
 /* dx[N,H,W,C] = adjoint of ledn_bilinear (gather form, deterministic); dy [N,Ho,Wo,C]. */
 int ledn_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, int C, int Ho, int Wo,

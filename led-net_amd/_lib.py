@@ -200,6 +200,7 @@ _PROTOS = {
     'ledn_dwconv2d_bwd_weight': ([C.POINTER(DwBwdDesc), vp], i32),
     'ledn_sesp_pyramid_bwd_data': ([C.POINTER(PyrBwdDesc), vp], i32),
     'ledn_sesp_pyramid_bwd_weight': ([C.POINTER(PyrBwdDesc), vp], i32),
+    'ledn_sesp_pyramid_bwd_kernel_id': ([C.POINTER(PyrBwdDesc)], i32),
     'ledn_bilinear_bwd': ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     'ledn_avgpool3x3s2_bwd': ([vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     'ledn_window_attn_bwd': ([vp, fp, vp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp], i32),

@@ -4,6 +4,7 @@
 // per element, deterministic); only per-channel / per-tap reductions use f32
 // atomics (one per workgroup after an LDS reduction).
 #include "ledn_rt.h"
+#include "stencil.h"
 
 namespace ledn {
 
@@ -582,6 +583,8 @@ int dw3x3_bwd_weight_bf16(const ledn_dwbwd_desc& d, hipStream_t s);   // stencil
 int pyr_bwd_data_bf16(const ledn_pyrbwd_desc& d, hipStream_t s);
 bool pyr_tile_applies(const ledn_pyrbwd_desc& d);
 int pyr_bwd_data_tile(const ledn_pyrbwd_desc& d, hipStream_t s);
+bool pyr_ctx_applies(const ledn_pyrbwd_desc& d);
+int pyr_bwd_data_ctx(const ledn_pyrbwd_desc& d, hipStream_t s);
 int pyr_bwd_weight_bf16(const ledn_pyrbwd_desc& d, hipStream_t s);
 
 int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
@@ -777,6 +780,7 @@ int pyr_bwd_data_impl(const ledn_pyrbwd_desc& d, hipStream_t s) {
     const int cvn = v4 ? d.n / 4 : d.n;
     const long npo = (long)d.N * d.Ho * d.Wo;
     if (pyr_tile_applies(d)) return pyr_bwd_data_tile(d, s);
+    if (pyr_ctx_applies(d)) return pyr_bwd_data_ctx(d, s);
     if (d.dtype == LEDN_BF16 && v4 && d.stride == 1) {   // suffix sums, then the vectorised gather
         LEDN_LAUNCH((pyr_suffix_kernel<bf16_t, 4>), dim3((unsigned)cdiv(npo * cvn, 256)), dim3(256), 0, s,
                     (const bf16_t*)d.dy, (bf16_t*)d.gsum, npo, d.n);
@@ -798,6 +802,19 @@ int pyr_bwd_data_impl(const ledn_pyrbwd_desc& d, hipStream_t s) {
     else LEDN_K(bf16_t);
 #undef LEDN_K
     return check_launch();
+}
+
+// which kernel pyr_bwd_data_impl launches for d: 0 pyr_bwd_data_kernel, 1 pyr_bwd_data_bf16_kernel (both after
+// pyr_suffix_kernel), 2 pyr_bwd_data_tile_kernel, 3 pyr_bwd_data_ctx_kernel (both straight from dy)
+int pyr_bwd_data_kernel_id(const ledn_pyrbwd_desc& d) {
+    if (pyrbwd_validate(d) != LEDN_OK) return -1;
+    if (pyr_tile_applies(d)) return 2;
+    if (pyr_ctx_applies(d)) return 3;
+    const int cvn = d.n / 8;
+    return d.dtype == LEDN_BF16 && d.stride == 1 && d.n % 8 == 0 && 256 % cvn == 0 && cvn <= 256 &&
+                   (long)d.N * d.H * d.W * d.n * 4 < (1L << 31)
+               ? 1
+               : 0;
 }
 
 int pyr_bwd_weight_impl(const ledn_pyrbwd_desc& d, hipStream_t s) {
@@ -1064,10 +1081,78 @@ __global__ void __launch_bounds__(256) avgpool3x3s2_bwd_kernel(const T* dy, cons
     stv<V>(dx + pix * C + c, acc);
 }
 
+// The same adjoint at 16 bytes per lane (bf16, C = 8 * 2^k <= 2048): a lane owns 8 channels of one dy pixel's 2 x 2 quad of
+// dx, whose taps are dy[qy .. qy+1][qx .. qx+1] -- four pieces in, four addends in, four stores, no divergence, a pixel
+// cursor instead of a 64-bit index split per element.  The sums keep the order of the kernel above (kh outer, kw inner,
+// then * 1/9, then + add), so the result is bit-identical; a piece outside dy enters as +0.
+__global__ void __launch_bounds__(256) avgpool3x3s2_bwd_quad_kernel(const bf16_t* dy, const bf16_t* add, bf16_t* dx, int N,
+                                                                    int H, int W, int C, int Ho, int Wo) {
+    const int cvn = C / 8, rows = 256 / cvn;
+    const int r = threadIdx.x / cvn, c = (threadIdx.x % cvn) * 8;
+    const long nq = (long)N * Ho * Wo;
+    const long ppb = cdiv(cdiv(nq, (long)gridDim.x), (long)rows) * rows;
+    const long p0 = (long)xcd_block(blockIdx.x, gridDim.x) * ppb, p1 = min(nq, p0 + ppb);
+    PixCursor cur;
+    cur.init(p0 + r, Ho, Wo);
+    for (long p = p0 + r; p < p1; p += rows, cur.advance(rows, Ho, Wo)) {
+        const bool xr = cur.x + 1 < Wo, yb = cur.y + 1 < Ho;
+        const unsigned gb = (unsigned)(p * C + c);
+        uint4 raw[4];                                        // dy[qy][qx], [qy][qx+1], [qy+1][qx], [qy+1][qx+1]
+        raw[0] = *reinterpret_cast<const uint4*>(dy + gb);
+        raw[1] = ld_tap(dy, gb + (unsigned)C, gb, xr);
+        raw[2] = ld_tap(dy, gb + (unsigned)(Wo * C), gb, yb);
+        raw[3] = ld_tap(dy, gb + (unsigned)((Wo + 1) * C), gb, xr && yb);
+        float g[4][8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned u[4] = {raw[k].x, raw[k].y, raw[k].z, raw[k].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                g[k][2 * i] = __uint_as_float(u[i] << 16);
+                g[k][2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
+            }
+        }
+        const int y0 = 2 * cur.y, x0 = 2 * cur.x;
+        const unsigned ob = (unsigned)((((long)cur.n * H + y0) * W + x0) * C + c);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int py = q >> 1, px = q & 1;
+            if (y0 + py >= H || x0 + px >= W) continue;
+            float acc[8];
+#pragma unroll
+            for (int v = 0; v < 8; ++v) {
+                acc[v] = 0.f;
+                if (py && px) acc[v] += g[3][v];
+                if (py) acc[v] += g[2][v];
+                if (px) acc[v] += g[1][v];
+                acc[v] += g[0][v];
+            }
+#pragma unroll
+            for (int v = 0; v < 8; ++v) acc[v] *= (1.f / 9.f);
+            const unsigned o = ob + (unsigned)((py * W + px) * C);
+            if (add) {
+                float a[8];
+                ldv<8>(add + o, a);
+#pragma unroll
+                for (int v = 0; v < 8; ++v) acc[v] += a[v];
+            }
+            stv<8>(dx + o, acc);
+        }
+    }
+}
+
 int avgpool3x3s2_bwd_impl(const void* dy, const void* add, void* dx, int N, int H, int W, int C, int Ho,
                           int Wo, int dtype, hipStream_t s) {
     LEDN_REQUIRE(dy && dx && N > 0 && H > 0 && W > 0 && C > 0);
     LEDN_REQUIRE(Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1);
+    if ((options().stream_fast & 2) && dtype == LEDN_BF16 && C % 8 == 0 && 256 % (C / 8) == 0 && C <= 2048 &&
+        (long)N * H * W * C < (1L << 31)) {
+        long nb = cdiv((long)N * Ho * Wo, (256 / (C / 8)) * 2);
+        if (nb > 2048) nb = 2048;
+        LEDN_LAUNCH(avgpool3x3s2_bwd_quad_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)add,
+                    (bf16_t*)dx, N, H, W, C, Ho, Wo);
+        return check_launch();
+    }
     const bool v4 = C % 4 == 0;
     const long total = (long)N * H * W * (v4 ? C / 4 : C);
     const dim3 grid((unsigned)cdiv(total, 256));

@@ -94,6 +94,7 @@ int dw_bwd_data_impl(const ledn_dwbwd_desc& d, hipStream_t s);
 int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s);
 int pyr_bwd_data_impl(const ledn_pyrbwd_desc& d, hipStream_t s);
 int pyr_bwd_weight_impl(const ledn_pyrbwd_desc& d, hipStream_t s);
+int pyr_bwd_data_kernel_id(const ledn_pyrbwd_desc& d);
 int bilinear_bwd_impl(const void* dy, void* dx, int N, int H, int W, int C, int Ho, int Wo, int dtype_dy,
                       int dtype_dx, hipStream_t s);
 int avgpool3x3s2_bwd_impl(const void* dy, const void* add, void* dx, int N, int H, int W, int C, int Ho,
@@ -512,6 +513,7 @@ int ledn_sesp_pyramid_bwd_data(const ledn_pyrbwd_desc* d, void* stream) {
 int ledn_sesp_pyramid_bwd_weight(const ledn_pyrbwd_desc* d, void* stream) {
     return d ? pyr_bwd_weight_impl(*d, S(stream)) : LEDN_EINVAL;
 }
+int ledn_sesp_pyramid_bwd_kernel_id(const ledn_pyrbwd_desc* d) { return d ? pyr_bwd_data_kernel_id(*d) : -1; }
 int ledn_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, int C, int Ho, int Wo, int dtype_dy,
                       int dtype_dx, void* stream) {
     return bilinear_bwd_impl(dy, dx, N, H, W, C, Ho, Wo, dtype_dy, dtype_dx, S(stream));

@@ -300,6 +300,189 @@ int pyr_bwd_data_tile(const ledn_pyrbwd_desc& d, hipStream_t s) {
     return check_launch();
 }
 
+// Unequal dilations (the context branch: [1,2,3,4]), stride 1 or 2, any map size: the data gradient straight from dy
+// with the dy patch staged ONCE in LDS -- no suffix-sum launch, no gsum, none of the 36 global tap loads per output.
+// Workgroup = 256 lanes = a 16 x 16-pixel tile of dy (= 16 S x 16 S pixels of dx) x 16 channels.  Branch b keeps its own
+// patch [16 + 2 h_b]^2 x 16 channels with halo h_b = dil_b (stride 1) or ceil(dil_b / 2) (stride 2): for [1,2,3,4]
+// 1784 pixels x 32 B = 55.75 KB at stride 1 (two workgroups per CU), 1448 pixels = 45.25 KB at stride 2 (three).  The
+// lane that stages a dy pixel loads the pieces of the branches that need it (a pixel r rings outside the tile serves
+// only the branches with h_b >= r, and the suffix sum of branch b needs only dy_b .. dy_3; all of a lane's up to 20
+// loads are in flight together), forms g_b = sum_{b' >= b} dy_b' in f32 and stores it rounded to bf16 -- bit for bit
+// what pyr_suffix_kernel leaves in gsum.  Gather: lane = (column, 8-channel group, 2 tile rows); per (branch, tap) the 8
+// filter values are read once from LDS and feed both rows.  Stride 2: the four parities of dx are handled one after
+// another (wave-uniform), each accumulating only the taps the stride leaves on the lattice (20 / 4 / 4 / 8 of 36 for
+// [1,2,3,4]); a tap's offset in the patch is a constant of (parity, tap), no division per element.
+// The taps are accumulated in the order of the kernels this one replaces (pyr_bwd_data_bf16_kernel at stride 1,
+// pyr_bwd_data_kernel at stride 2), so dx is bit-identical to theirs.
+// 128 lanes x 4 rows (one wave per SIMD) with the staging in three dependent rounds ran at 66 us where this form takes 50
+// (16 x 128 x 128 x 32, stride 1); before the reads of a tap group were issued together it took 78.
+constexpr int PYC_T = 16;
+constexpr int PYC_MAXPIX1 = 1784, PYC_MAXPIX2 = 1448;    // patch pixels of [1,2,3,4]: halos 1,2,3,4 / 1,1,2,2
+static __host__ __device__ __forceinline__ int pyc_halo(int dl, int stride) { return stride == 1 ? dl : (dl + 1) / 2; }
+
+template <int S>
+__global__ void __launch_bounds__(256) pyr_bwd_data_ctx_kernel(ledn_pyrbwd_desc d) {
+    constexpr int T = PYC_T, NT = 256, R = 2, NB = 5;   // lanes, tile rows per lane, staged pieces in flight per lane
+    __shared__ __attribute__((aligned(16))) unsigned char s_g[(S == 1 ? PYC_MAXPIX1 : PYC_MAXPIX2) * 32];   // per branch [row][column][half] x 16 B
+    __shared__ __attribute__((aligned(16))) float s_w[36 * 16];
+    const int tid = threadIdx.x;
+    const int cw = d.n % 16 == 0 ? 16 : 8, nc = d.n / cw;       // channels per workgroup
+    const int tx = (d.Wo + T - 1) / T, ty = (d.Ho + T - 1) / T;
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);
+    const int cgp = (int)(bid % (unsigned)nc);
+    const unsigned tile = bid / (unsigned)nc;
+    const int txi = (int)(tile % (unsigned)tx), tyi = (int)((tile / (unsigned)tx) % (unsigned)ty);
+    const int img = (int)(tile / (unsigned)(tx * ty));
+    const int c0 = cgp * cw, n4 = 4 * d.n;
+    int hb[4], pw[4], pb[4], hm = 0;
+    {
+        int run = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            hb[b] = pyc_halo(d.dil[b], S);
+            pw[b] = T + 2 * hb[b];
+            pb[b] = run;
+            run += pw[b] * pw[b];
+            hm = max(hm, hb[b]);
+        }
+    }
+    const int pm = T + 2 * hm, nitem = pm * pm * 2;
+    const int cy0 = tyi * T, cx0 = txi * T;
+    const bf16_t* dy = reinterpret_cast<const bf16_t*>(d.dy) + (long)img * d.Ho * d.Wo * n4 + c0;
+    for (int i = tid; i < 36 * 16; i += NT) {
+        const int cc = i & 15;
+        s_w[i] = cc < cw ? d.w[(long)(i >> 4) * d.n + c0 + cc] : 0.f;
+    }
+#pragma unroll 1
+    for (int e0 = tid; e0 < nitem; e0 += NB * NT) {      // (one pass: 1152 pieces at halo 4)
+        uint4 raw[NB][4];
+        int mr[NB], mq[NB];                                   // ring of the staged pixel (-1: nothing to do), patch position
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int e = e0 + i * NT, half = e & 1, q = e >> 1;
+            const int py = q / pm, px = q - py * pm;
+            const int gy = cy0 - hm + py, gx = cx0 - hm + px;
+            const int r = max(max(max(cy0 - gy, gy - (cy0 + T - 1)), max(cx0 - gx, gx - (cx0 + T - 1))), 0);
+            int bmin = 4;
+#pragma unroll
+            for (int b = 3; b >= 0; --b)
+                if (hb[b] >= r) bmin = b;
+            const bool act = e < nitem && half * 8 < cw && bmin < 4;
+            const bool ok = act && gy >= 0 && gy < d.Ho && gx >= 0 && gx < d.Wo;
+            const bf16_t* src = dy + ((long)gy * d.Wo + gx) * n4 + half * 8;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                raw[i][b] = (ok && b >= bmin) ? *reinterpret_cast<const uint4*>(src + b * d.n) : uint4{0u, 0u, 0u, 0u};
+            mr[i] = act ? r : -1;
+            mq[i] = (py << 8) | (px << 1) | half;
+        }
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            if (mr[i] < 0) continue;
+            const int half = mq[i] & 1, px = (mq[i] >> 1) & 127, py = mq[i] >> 8;
+            f32x2_t run[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) run[k] = f32x2_t{0.f, 0.f};
+#pragma unroll
+            for (int b = 3; b >= 0; --b) {
+                f32x2_t tv[4];
+                bf16x8_unpack(raw[i][b], tv);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) run[k] += tv[k];
+                if (hb[b] >= mr[i]) {
+                    const int row = py - hm + hb[b], col = px - hm + hb[b];
+                    *reinterpret_cast<uint4*>(s_g + ((long)(pb[b] + row * pw[b] + col) * 2 + half) * 16) = bf16x8_pack(run);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int cg = tid & 1, lx = (tid >> 1) & 15, yg = tid >> 5;   // 8 row groups of R rows
+    if (cg * 8 >= cw) return;
+    bf16_t* dx = reinterpret_cast<bf16_t*>(d.dx) + (long)img * d.H * d.W * d.n + c0 + cg * 8;
+#pragma unroll 1
+    for (int cls = 0; cls < S * S; ++cls) {
+        const int py = cls / S, px = cls % S;               // parity of the dx pixels of this pass
+        f32x2_t acc[R][4];
+#pragma unroll
+        for (int yo = 0; yo < R; ++yo)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[yo][i] = f32x2_t{0.f, 0.f};
+        int pbb = 0;
+#pragma unroll 1
+        for (int b = 0; b < 4; ++b) {                       // (a real loop: unrolled, the FMA chains sink below all 144 reads)
+            const int dl = d.dil[b], hbb = pyc_halo(dl, S), pwb = T + 2 * hbb;
+            const unsigned char* pbase = s_g + ((long)(pbb + (yg * R + hbb) * pwb + lx + hbb) * 2 + cg) * 16;
+            const float* wb = s_w + b * 9 * 16 + cg * 8;
+            // the reads of one group of taps (a filter row at stride 1, one tap at stride 2, where the lattice test is
+            // per tap) are issued together, then consumed: left to itself the compiler waits for every read in turn
+            // (216 LDS round trips per lane with one wave per SIMD to hide them)
+            constexpr int G = S == 1 ? 3 : 1;
+#pragma unroll
+            for (int t0 = 0; t0 < 9; t0 += G) {
+                if (S == 2) {
+                    const int th = py - (t0 / 3 - 1) * dl, tw = px - (t0 % 3 - 1) * dl;
+                    if ((th | tw) & 1) continue;                                 // off the stride's lattice (wave-uniform)
+                }
+                uint4 rg[G][R];
+                f32x2_t wv[G][4];
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    const int t = t0 + j, kh = S == 1 ? 2 - t / 3 : t / 3, kw = S == 1 ? 2 - t % 3 : t % 3;
+                    const int oh = (py - (kh - 1) * dl) / S, ow = (px - (kw - 1) * dl) / S;   // dy pixel = tile pixel + (oh, ow)
+                    const unsigned char* p = pbase + (oh * pwb + ow) * 32;
+#pragma unroll
+                    for (int yo = 0; yo < R; ++yo) rg[j][yo] = *reinterpret_cast<const uint4*>(p + yo * pwb * 32);
+                    f32x8_load(wb + (kh * 3 + kw) * 16, wv[j]);
+                }
+                sched_fence();
+#pragma unroll
+                for (int j = 0; j < G; ++j)
+#pragma unroll
+                    for (int yo = 0; yo < R; ++yo) {
+                        f32x2_t gv[4];
+                        bf16x8_unpack(rg[j][yo], gv);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) acc[yo][i] = pk_fma(gv[i], wv[j][i], acc[yo][i]);
+                    }
+                sched_fence();
+            }
+            pbb += pwb * pwb;
+        }
+        const int gx = (cx0 + lx) * S + px;
+#pragma unroll
+        for (int yo = 0; yo < R; ++yo) {
+            const int gy = (cy0 + yg * R + yo) * S + py;
+            if (gy < d.H && gx < d.W) *reinterpret_cast<uint4*>(dx + ((long)gy * d.W + gx) * d.n) = bf16x8_pack(acc[yo]);
+        }
+    }
+}
+
+// the context-branch tile kernel applies (like pyr_tile_applies: gsum is then neither written nor read).  Dilations in
+// any order; the patches of the four branches must fit the LDS image sized for [1,2,3,4] at stride 1.
+bool pyr_ctx_applies(const ledn_pyrbwd_desc& d) {
+    if (!(options().stream_fast & 2) || d.dtype != LEDN_BF16 || d.n % 8 || !pow2(d.n / 8) || d.n > 512 ||
+        (long)d.N * d.H * d.W * d.n * 4 >= (1L << 31) || pyr_tile_applies(d))
+        return false;
+    int pix = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int h = pyc_halo(d.dil[b], d.stride);
+        if (h > 4) return false;
+        pix += (PYC_T + 2 * h) * (PYC_T + 2 * h);
+    }
+    return pix <= (d.stride == 1 ? PYC_MAXPIX1 : PYC_MAXPIX2);
+}
+
+int pyr_bwd_data_ctx(const ledn_pyrbwd_desc& d, hipStream_t s) {
+    const long nb = (long)d.N * cdiv(d.Ho, PYC_T) * cdiv(d.Wo, PYC_T) * (d.n / (d.n % 16 == 0 ? 16 : 8));
+    if (d.stride == 1) LEDN_LAUNCH(pyr_bwd_data_ctx_kernel<1>, dim3((unsigned)nb), dim3(256), 0, s, d);
+    else LEDN_LAUNCH(pyr_bwd_data_ctx_kernel<2>, dim3((unsigned)nb), dim3(256), 0, s, d);
+    return check_launch();
+}
+
+// one of the two tiled data gradients served the call: no gsum, the weight gradient forms its suffix sums from dy
+bool pyr_from_dy(const ledn_pyrbwd_desc& d) { return pyr_tile_applies(d) || pyr_ctx_applies(d); }
+
 // gsum holds the suffix sums g_b = sum_{b' >= b} dy_b' (pyr_suffix_kernel)
 __global__ void __launch_bounds__(256) pyr_bwd_data_bf16_kernel(ledn_pyrbwd_desc d) {
     constexpr int V = 8;
@@ -393,9 +576,17 @@ __global__ void __launch_bounds__(256) pyr_bwd_weight_bf16_kernel(ledn_pyrbwd_de
             if (from_dy) {      // g_b = sum_{b' >= b} dy_b' formed here (the tiled data gradient leaves no gsum behind)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) gv[i] = f32x2_t{0.f, 0.f};
-                for (int bb = 3; bb >= b; --bb) {
+                // four unconditional loads in flight with the nine taps (a branch below b re-reads piece b and counts as
+                // zero): 2 - 3 us per launch faster than a loop of 4 - b dependent trips on the context branch's shapes
+                const unsigned gb = (unsigned)(p * (4L * d.n) + c);
+                uint4 rw[4];
+#pragma unroll
+                for (int bb = 0; bb < 4; ++bb)
+                    rw[bb] = ld_tap(g, gb + (unsigned)(bb * d.n), gb + (unsigned)(b * d.n), bb >= b);
+#pragma unroll
+                for (int bb = 3; bb >= 0; --bb) {
                     f32x2_t tv[4];
-                    bf16x8_unpack(*reinterpret_cast<const uint4*>(g + p * (4L * d.n) + (long)bb * d.n + c), tv);
+                    bf16x8_unpack(rw[bb], tv);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) gv[i] += tv[i];
                 }
@@ -555,7 +746,7 @@ int pyr_bwd_weight_bf16(const ledn_pyrbwd_desc& d, hipStream_t s) {
     float* part = (nb > 32 || det()) ? ws_take(nb * 36 * d.n) : nullptr;
     if (!part && nb > 128) nb = 128;
     LEDN_LAUNCH(pyr_bwd_weight_bf16_kernel, dim3((unsigned)nb, 4u), dim3(256), (size_t)(36 * d.n) * sizeof(float), s, d,
-                part, pyr_tile_applies(d));
+                part, pyr_from_dy(d));
     if (part) return finish_partials(part, (int)nb, 36 * d.n, 1, d.dw, nullptr, nullptr, s);
     return check_launch();
 }

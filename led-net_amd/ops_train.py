@@ -328,6 +328,23 @@ def dw_unpack_grad(weights, sinks, dpacked, stacked):
          work=_ops._TIMING is not None and (f'dwunpack {tuple(dpacked.shape)}', 12 * dpacked.numel(), 0))
 
 
+PYR_BWD_KERNELS = ('pyr_bwd_data_kernel', 'pyr_bwd_data_bf16_kernel', 'pyr_bwd_data_tile_kernel', 'pyr_bwd_data_ctx_kernel')
+
+
+def sesp_pyramid_bwd_kernel_id(x, dy, dil, stride):
+    """which kernel ledn_sesp_pyramid_bwd_data runs these arguments on (no launch): index into PYR_BWD_KERNELS; the first
+    two follow pyr_suffix_kernel and read its gsum, the last two read dy itself (include/ledn.h)"""
+    lib = _lib.get_lib()
+    d = _lib.PyrBwdDesc()
+    N, H, W, n = x.shape
+    d.x, d.dy, d.gsum, d.dx = _p(x), _p(dy), _p(dy), _p(x)     # only tested for NULL
+    d.N, d.H, d.W, d.n, d.Ho, d.Wo, d.stride = N, H, W, n, dy.shape[1], dy.shape[2], stride
+    for i in range(4):
+        d.dil[i] = dil[i]
+    d.dtype = _dt(x)
+    return int(lib.cdll.ledn_sesp_pyramid_bwd_kernel_id(d))
+
+
 def sesp_pyramid_bwd(x, dy, w_b33n, dil, stride, dw_out=None):
     """-> (dx [N,H,W,n], dw [4,3,3,n]); dw_out: f32 buffer the weight gradient is accumulated into."""
     lib = _lib.get_lib()
@@ -346,9 +363,15 @@ def sesp_pyramid_bwd(x, dy, w_b33n, dil, stride, dw_out=None):
     for i in range(4):
         d.dil[i] = dil[i]
     d.dtype = _dt(x)
-    _run(lib, 'ledn_sesp_pyramid_bwd_data', x, d, work=_ops._TIMING is not None and (f'pyrbwd_data n{n} {tuple(x.shape)}', _nb(dy, gsum, gsum, dx), 2 * dy.numel() * 9))
+    timing = _ops._TIMING is not None
+    kid = lib.cdll.ledn_sesp_pyramid_bwd_kernel_id(d) if timing else 0
+    from_dy = kid >= 2          # the tiled data gradients: gsum is neither written nor read
+    _run(lib, 'ledn_sesp_pyramid_bwd_data', x, d, work=timing and (
+        f'pyrbwd_data n{n} {tuple(x.shape)}', _nb(dy, dx) if from_dy else _nb(dy, gsum, gsum, dx), 2 * dy.numel() * 9,
+        PYR_BWD_KERNELS[kid]))
     with _on_side_stream(x, dw_out, x, dy, gsum, dw):
-        _run(lib, 'ledn_sesp_pyramid_bwd_weight', x, d, work=_ops._TIMING is not None and (f'pyrbwd_w n{n} {tuple(x.shape)}', _nb(x, gsum), 2 * dy.numel() * 9))
+        _run(lib, 'ledn_sesp_pyramid_bwd_weight', x, d, work=timing and (
+            f'pyrbwd_w n{n} {tuple(x.shape)}', _nb(x, dy) if from_dy else _nb(x, gsum), 2 * dy.numel() * 9))
     return dx, dw
 
 
