@@ -919,6 +919,37 @@ int ledn_tversky_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int
                              void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * LovaszLoss, the multi-class Lovasz-Softmax form (mmseg/models/losses/lovasz_loss.py:129-222), on NHWC f32 logits
+ * [N][HW][C] and int64 labels [N][HW] (csrc/lovasz.hip).  Valid pixels: label != ignore_index.  For each class c of the
+ * loss: fg = (label == c) (a label >= C that is not ignore_index is background for every class), e = |fg -
+ * softmax(logits)_c|, the valid pixels ranked by descending e -- over the whole batch, or per image with per_image --
+ * and loss_c = sum_i e_(i) g_i, g the increment of the Jaccard index along that order, formed in closed form from exact
+ * integer counts: with G the class's foreground count and F / B the foreground / background elements before position
+ * i, U = G + B, I = G - F, g = 1 / U on a foreground element, I / (U (U + 1)) on a background one, 1 for U = 0.
+ * mode: 0 every class, 1 the classes with a foreground pixel ('present'; per image with per_image), 2 the n_classes
+ * distinct classes listed in `classes` (HOST memory, read during the call; NULL otherwise).  class_weight [C] f32 on
+ * the device or NULL multiplies loss_c.  The segment's loss is the mean of loss_c over the classes computed;
+ * per_image: out[0] = loss_weight * mean (reduction 0) or sum (1) of the N per-image losses; else out[0] = loss_weight
+ * * that mean.  No valid pixel, or no class computed: that loss is 0 and its gradient 0.
+ * Ranking: a stable least-significant-digit radix sort (4 passes of 8 bits) of (key, pixel index) pairs, key =
+ * ((bits(e) << 1) | fg) + 1 with e clamped to [0, 1] (at most 0x7F000002; 0 = ignored pixel, sorted behind everything)
+ * taken in descending order.  Ties: descending error, then foreground first, then lower pixel index; the loss does not
+ * depend on the order inside a run of equal errors, the gradient is the subgradient of this order.  Bit-reproducible: no
+ * float atomics, no waiting between workgroups; the launch sequence depends on the sizes only (hipGraph-capturable).
+ * out[4]: loss, top-1 accuracy in percent over the valid pixels (as the CE / Dice entry points), the divisor of the
+ * mean (the number of classes computed; per_image: N or 1), the number of valid pixels.
+ * work: ledn_lovasz_work_bytes(N, HW, C, per_image) bytes, 16-byte aligned (0 for sizes outside the limits): two key and
+ * two index buffers, the per-pixel g, the unscaled logit gradient [N*HW][C] (starting at byte 16, whatever per_image)
+ * and the per-tile counts; (20 + 4 C) N HW bytes and change.  The backward is dlogits = that gradient * dloss[0] *
+ * loss_weight / out[2], from work and out alone.  Limits: 2 <= C <= 1024, N <= 65535, N*HW < 2^31. */
+long long ledn_lovasz_work_bytes(long long N, long long HW, int C, int per_image);
+int ledn_lovasz_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C,
+                         const float* class_weight, const int* classes, int n_classes, int mode, int per_image,
+                         int reduction, int ignore_index, float loss_weight, float* work, float* out, void* stream);
+int ledn_lovasz_loss_bwd(const float* work, const float* out, const float* dloss, int N, long long HW, int C,
+                         float* dlogits, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The four pooled-context MLPs of Muti_AFF (classification/model_utils.py:377-400: AdaptiveAvgPool2d(S) ->
  * Conv1x1(C->Ci)+bias -> BatchNorm -> ReLU -> Conv1x1(Ci->C)+bias -> [BatchNorm: in the gate kernel], S = 4, 8, 16, 1)
  * as ONE launch sequence for all four scales: they are chains of tiny launch-bound kernels (~50 launches per

@@ -247,6 +247,10 @@ _PROTOS = {
     'ledn_tversky_loss_up_fwd': ([fp, i32, i32, i32, i32, i32, vp, fp, C.c_float, C.c_float, C.c_float, i32, i32, C.c_float, fp, fp,
                                   vp], i32),
     'ledn_tversky_loss_up_bwd': ([fp, i32, i32, i32, i32, i32, vp, i32, fp, fp, fp, fp, vp], i32),
+    # LovaszLoss (lovasz.hip)
+    'ledn_lovasz_work_bytes': ([i64, i64, i32, i32], i64),
+    'ledn_lovasz_loss_fwd': ([fp, vp, i32, i64, i32, fp, vp, i32, i32, i32, i32, i32, C.c_float, fp, fp, vp], i32),
+    'ledn_lovasz_loss_bwd': ([fp, fp, fp, i32, i64, i32, fp, vp], i32),
     'ledn_sgd_step': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, vp], i32),
     'ledn_grad_norm_partials': ([fp, i64, i32, fp, i32, vp], i32),
     'ledn_sgd_step_clip': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, fp, i32, i32, C.c_float, C.c_float,

@@ -139,6 +139,12 @@ int seg_loss_up_fwd_impl(int kind, const float* src, int N, int Hs, int Ws, int 
 int seg_loss_up_bwd_impl(int kind, const float* src, int N, int Hs, int Ws, int H, int W, const long long* target,
                          const SlCfg& q, const float* work, const float* out, const float* dloss, float* dsrc,
                          hipStream_t s);
+long long lovasz_work_bytes(long long N, long long HW, int C, int per_image);
+int lovasz_fwd_impl(const float* logits, const long long* target, int N, long long HW, int C, const float* cw,
+                    const int* classes, int nlist, int mode, int per_image, int reduction, int ignore_index,
+                    float loss_weight, float* work, float* out, hipStream_t s);
+int lovasz_bwd_impl(const float* work, const float* out, const float* dloss, int N, long long HW, int C, float* dlogits,
+                    hipStream_t s);
 int tta_accumulate_impl(const ledn_tta_desc& d, hipStream_t s);
 int slide_accumulate_impl(float* canvas, const float* crop, int N, int C, int H, int W, int y1, int x1, int hc, int wc,
                           int crop_planar, hipStream_t s);
@@ -739,6 +745,19 @@ int ledn_tversky_loss_up_bwd(const float* src, int N, int Hs, int Ws, int H, int
     return seg_loss_up_bwd_impl(SL_TVERSKY, src, N, Hs, Ws, H, W, target,
                                 sl_tversky_cfg(nullptr, 0.f, 0.f, 0.f, ignore_index, -1, 1.f), work, out, dloss, dsrc,
                                 S(stream));
+}
+long long ledn_lovasz_work_bytes(long long N, long long HW, int C, int per_image) {
+    return lovasz_work_bytes(N, HW, C, per_image);
+}
+int ledn_lovasz_loss_fwd(const float* logits, const long long* target, int N, long long HW, int C,
+                         const float* class_weight, const int* classes, int n_classes, int mode, int per_image,
+                         int reduction, int ignore_index, float loss_weight, float* work, float* out, void* stream) {
+    return lovasz_fwd_impl(logits, target, N, HW, C, class_weight, classes, n_classes, mode, per_image, reduction,
+                           ignore_index, loss_weight, work, out, S(stream));
+}
+int ledn_lovasz_loss_bwd(const float* work, const float* out, const float* dloss, int N, long long HW, int C,
+                         float* dlogits, void* stream) {
+    return lovasz_bwd_impl(work, out, dloss, N, HW, C, dlogits, S(stream));
 }
 int ledn_sgd_step(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,
                   const float* lr_dev, float momentum, float weight_decay, float grad_scale, void* stream) {

@@ -163,6 +163,37 @@ __device__ __forceinline__ float wave_min(float v) {
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 
+// the lanes of the wave whose `ok` is set and whose 8-bit digit d equals this lane's (a lane whose own `ok` is clear gets
+// an unspecified mask); every lane of the wave must call.  Nine ballots on the device; the emulation build compares the
+// 64 exchanged values directly (its __ballot costs 64 exchanges)
+#ifdef LEDN_CPU_EMU
+__device__ __forceinline__ unsigned long long wave_match8(unsigned d, bool ok) {
+    emu::Ctx& c = *LEDN_EMU_CUR;
+    const unsigned v = ok ? (d & 255u) : 0xffffffffu;
+    std::memcpy(c.xchg + c.lane * 64, &v, 4);
+    emu::barrier_wait(c.wave_bar);
+    unsigned long long m = 0ull;
+    for (int l = 0; l < 64; ++l) {
+        unsigned x;
+        std::memcpy(&x, c.xchg + l * 64, 4);
+        if (x == v) m |= 1ull << l;
+    }
+    emu::barrier_wait(c.wave_bar);
+    return m;
+}
+#else
+__device__ __forceinline__ unsigned long long wave_match8(unsigned d, bool ok) {
+    unsigned long long m = __ballot(ok);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const bool bit = (d >> b) & 1u;
+        const unsigned long long bal = __ballot(bit);
+        m &= bit ? bal : ~bal;
+    }
+    return m;
+}
+#endif
+
 // dynamically sized LDS (the launch's shared-memory argument), 16-byte aligned
 #ifdef LEDN_CPU_EMU
 #define LEDN_DYN_SHARED(T, name) T* name = reinterpret_cast<T*>(LEDN_DYN_SMEM)

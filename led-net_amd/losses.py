@@ -1,4 +1,4 @@
-"""OhemCrossEntropy, CrossEntropyLoss, DiceLoss, FocalLoss and TverskyLoss (registered under the reference's names)
+"""OhemCrossEntropy, CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss and LovaszLoss (registered under the reference's names)
 and accuracy.
 
 Mirrors mmseg/models/losses/ohem_cross_entropy_loss.py:11-94 (constructor
@@ -16,6 +16,9 @@ pass + a fixed-order finish, the divisor formed on the device, nothing per-pixel
 
 FocalLoss (sigmoid form) and TverskyLoss mirror losses/focal_loss.py:136-337 and losses/tversky_loss.py:60-137 in the
 same way, on further kernels of csrc/seg_loss.hip; DESIGN.md "FocalLoss and TverskyLoss in the head".
+
+LovaszLoss (the multi-class Lovasz-Softmax form) mirrors losses/lovasz_loss.py:225-323; its arithmetic is the on-device
+radix sort and closed-form Lovasz gradient of csrc/lovasz.hip; DESIGN.md "LovaszLoss in the head".
 """
 import math
 
@@ -267,6 +270,73 @@ class TverskyLoss(_ClassWeighted):
         """pred: N x C x H x W (any float layout), target: N x H x W int64."""
         from .train import seg_loss
         return seg_loss(self, pred, target, ignore_index)
+
+    @property
+    def loss_name(self):
+        return self._loss_name
+
+
+@MODELS.register_module()
+class LovaszLoss(_ClassWeighted):
+    """losses/lovasz_loss.py:225-323, ``loss_type='multi_class'`` (lovasz_softmax, :129-222).  As in the reference,
+    ``per_image=False`` requires ``reduction='none'`` (:269-271; the result is a scalar anyway) and ranks the valid
+    pixels of the whole batch; ``per_image=True`` ranks each image on its own and takes the 'mean' or 'sum' of the N
+    losses.  Without a valid pixel (in the batch, or in one image) that loss is 0, where the reference returns an empty
+    tensor or fails."""
+
+    def __init__(self, loss_type='multi_class', classes='present', per_image=False, reduction='mean', class_weight=None,
+                 loss_weight=1.0, loss_name='loss_lovasz'):
+        super().__init__()
+        if loss_type == 'binary':
+            raise NotImplementedError("LovaszLoss: loss_type='binary' (the hinge form on a one-channel head) is not "
+                                      "supported; use loss_type='multi_class'")
+        if loss_type != 'multi_class':
+            raise ValueError(f"LovaszLoss: loss_type={loss_type!r} should be 'binary' or 'multi_class'")
+        if isinstance(classes, str):
+            if classes not in ('all', 'present'):
+                raise ValueError(f"LovaszLoss: classes={classes!r} must be 'all', 'present' or a list of class indices")
+        elif (not isinstance(classes, (list, tuple)) or not classes
+              or not all(isinstance(c, int) and not isinstance(c, bool) and c >= 0 for c in classes)
+              or len(set(classes)) != len(classes)):
+            raise ValueError(f"LovaszLoss: classes={classes!r} must be 'all', 'present' or a non-empty list of distinct "
+                             f'class indices')
+        if per_image:
+            if reduction == 'none':
+                raise NotImplementedError("LovaszLoss: reduction='none' with per_image=True (one loss per image) is not "
+                                          "supported; use 'mean' or 'sum'")
+            if reduction not in ('mean', 'sum'):
+                raise ValueError(f"LovaszLoss: reduction={reduction!r} must be 'mean' or 'sum' with per_image=True")
+        elif reduction != 'none':
+            raise ValueError(f"LovaszLoss: reduction={reduction!r}: mmseg requires reduction='none' when per_image is "
+                             f'False (the loss is a scalar either way)')
+        if isinstance(class_weight, str):
+            raise TypeError(f'LovaszLoss: class_weight={class_weight!r}: a file path is not supported, give the list '
+                            f'of weights')
+        self.loss_type = loss_type
+        self.classes = list(classes) if isinstance(classes, tuple) else classes
+        self.per_image = bool(per_image)
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+        self._set_class_weight(class_weight)
+        self._loss_name = loss_name
+
+    def extra_repr(self):
+        return f'classes={self.classes!r}, per_image={self.per_image}, reduction={self.reduction!r}'
+
+    def kernel_args(self, logits, ignore_index):
+        """(family, keyword arguments of ops_train.lovasz_loss_fwd, of lovasz_loss_bwd) for channels-last `logits`"""
+        Cc = logits.shape[-1]
+        if not isinstance(self.classes, str) and not all(c < Cc for c in self.classes):
+            raise ValueError(f'{self.loss_name}: classes={self.classes!r} but the logits have {Cc} classes')
+        fwd = dict(loss_weight=self.loss_weight, classes=self.classes, per_image=self.per_image,
+                   reduction='mean' if self.reduction == 'none' else self.reduction, ignore_index=ignore_index,
+                   class_weight=self.class_weight_on(logits))
+        return 'lovasz', fwd, {}
+
+    def forward(self, cls_score, label, ignore_index=255, **kwargs):
+        """cls_score: N x C x H x W (any float layout), label: N x H x W int64."""
+        from .train import seg_loss
+        return seg_loss(self, cls_score, label, ignore_index)
 
     @property
     def loss_name(self):

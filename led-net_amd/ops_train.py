@@ -938,6 +938,78 @@ def tversky_loss_up_bwd(src, target, work, out, dloss, ignore_index=255):
     return _tversky_loss_bwd('tversky_loss_up_bwd', True, src, target, work, out, dloss, ignore_index)
 
 
+# --------------------------------------------------------------------------- #
+# LovaszLoss (csrc/lovasz.hip): an on-device radix sort of the per-class errors and the Lovasz gradient on top of it
+# --------------------------------------------------------------------------- #
+LOVASZ_TILE = 2048            # elements one workgroup ranks per scatter (csrc/lovasz.hip LV_TILE)
+LOVASZ_MAX_CLASSES = 1024
+_LOVASZ_MODES = {'all': 0, 'present': 1}
+
+
+def _lovasz_args(who, logits, target):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, False, 'mean')
+    if logits.shape[-1] > LOVASZ_MAX_CLASSES:
+        raise LednError(f'{who}: {logits.shape[-1]} classes; the Lovasz kernels take at most {LOVASZ_MAX_CLASSES}')
+    if P >= 1 << 31:
+        raise LednError(f'{who}: {P} pixels; N*H*W must stay below 2^31')
+    return lib, N, shape, P
+
+
+def _lovasz_classes(who, classes, Cc):
+    """'all' | 'present' | a non-empty list of distinct ints in [0, Cc) -> (mode, ctypes int array or None, its length)"""
+    if isinstance(classes, str):
+        if classes not in _LOVASZ_MODES:
+            raise LednError(f"{who}: classes={classes!r} ('all', 'present' or a list of class indices)")
+        return _LOVASZ_MODES[classes], None, 0
+    if (not isinstance(classes, (list, tuple)) or not classes
+            or not all(isinstance(c, int) and not isinstance(c, bool) for c in classes)):
+        raise LednError(f"{who}: classes={classes!r} ('all', 'present' or a non-empty list of class indices)")
+    if len(set(classes)) != len(classes) or not all(0 <= c < Cc for c in classes):
+        raise LednError(f'{who}: classes={list(classes)!r} must be distinct indices in [0, {Cc})')
+    return 2, (C.c_int * len(classes))(*classes), len(classes)
+
+
+def lovasz_loss_fwd(logits, target, loss_weight=1.0, classes='present', per_image=False, reduction='mean',
+                    ignore_index=255, class_weight=None):
+    """LovaszLoss (multi-class): logits [N,H,W,C] f32, target [N,H,W] int64 -> (out[4] = loss, acc, the divisor of the
+    mean, #valid pixels ; work, which holds the unscaled logit gradient for the backward).  classes: 'all', 'present'
+    or a list of class indices; per_image: rank and average per image, then reduction ('mean' | 'sum') over the images;
+    without it the ranking is over the batch and reduction is not used.  class_weight: None or [C] f32 on the device."""
+    who = 'lovasz_loss'
+    lib, N, shape, P = _lovasz_args(who, logits, target)
+    if reduction not in _REDUCTIONS:
+        raise LednError(f"{who}: reduction={reduction!r} (supported: 'mean' and 'sum' over the images of per_image)")
+    Cc = logits.shape[-1]
+    cw = _class_weight(class_weight, logits, Cc, who)
+    mode, arr, nlist = _lovasz_classes(who, classes, Cc)
+    nbytes = lib.cdll.ledn_lovasz_work_bytes(N, shape[1], Cc, int(bool(per_image)))
+    if nbytes <= 0:
+        raise LednError(f'{who}: shape outside the kernels\' limits')
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=logits.device)
+    out = torch.empty(4, dtype=torch.float32, device=logits.device)
+    _check(lib, logits, target, work, out)
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{Cc}', _nb(logits, target) + 100 * P, 60 * P * Cc, 'lv_scatter_kernel')
+    _run(lib, 'ledn_lovasz_loss_fwd', logits, _p(logits), _p(target), *shape, _p(cw), arr, nlist, mode, int(bool(per_image)),
+         _REDUCTIONS[reduction], int(ignore_index), float(loss_weight), _p(work), _p(out), work=timing)
+    return out, work
+
+
+def lovasz_loss_bwd(logits, target, work, out, dloss):
+    """-> dlogits = work's unscaled gradient * dloss * loss_weight / out[2] (one streaming kernel)"""
+    who = 'lovasz_loss_bwd'
+    lib, N, shape, P = _lovasz_args(who, logits, target)
+    Cc = logits.shape[-1]
+    if (not torch.is_tensor(work) or work.dtype != torch.float32 or work.dim() != 1
+            or work.numel() * 4 < lib.cdll.ledn_lovasz_work_bytes(N, shape[1], Cc, 0)):
+        raise LednError(f'{who}: work is not the forward\'s (too small for {N} images of {shape[1]} pixels and {Cc} classes)')
+    dl = torch.empty_like(logits)
+    dloss = dloss.reshape(1).to(torch.float32).contiguous()
+    _check(lib, logits, target, work, out, dloss, dl)
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{Cc}', 2 * _nb(dl), P * Cc, 'lv_bwd_kernel')
+    _run(lib, 'ledn_lovasz_loss_bwd', logits, _p(work), _p(out), _p(dloss), *shape, _p(dl), work=timing)
+    return dl
+
+
 def mfaf_ctx_fwd(pooled, seqs, training, stats1=None, momentum=0.1, tails=None, sync=None, world=1):
     """The four pooled-context MLPs of Muti_AFF in one launch sequence (ledn_mfaf_ctx_fwd).
     pooled: 4 f32 [N,S,S,C] maps; seqs: 4 x (conv1, bn1, conv2) modules.  -> (z2 list [N,S,S,C] f32, saved dict)

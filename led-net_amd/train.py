@@ -1388,10 +1388,13 @@ class OhemUp2Fn(Function):
 
 class SegLossFn(Function):
     """CrossEntropyLoss / DiceLoss / FocalLoss / TverskyLoss through csrc/seg_loss.hip: on NHWC logits (up = False) or
-    on resize(src -> label size) with the exact 2x resize folded into the kernels (up = True).  -> (loss, out[4])"""
+    on resize(src -> label size) with the exact 2x resize folded into the kernels (up = True).  LovaszLoss through
+    csrc/lovasz.hip, on NHWC logits only.  -> (loss, out[4])"""
 
     @staticmethod
     def forward(ctx, x, target, family, up, fwd_kw, bwd_kw):
+        if up and family == 'lovasz':
+            raise ValueError('LovaszLoss has no resize-folded form: it runs on the full-resolution logits')
         fwd = getattr(T, f'{family}_loss_up_fwd' if up else f'{family}_loss_fwd')
         out, work = fwd(x, target, **fwd_kw)
         ctx.save_for_backward(x, target, work, out)
@@ -1445,20 +1448,24 @@ def led_head_loss_by_feat(h, seg_logits, batch_data_samples):
     c0, c1 = h.loss_decode[0], h.loss_decode[1]
     H, W = hw
     fold = bool(FUSE_LOSS_RESIZE and H % 2 == 0 and W % 2 == 0 and xc.shape[-1] == 2)
-    from .losses import OhemCrossEntropy
+    from .losses import LovaszLoss, OhemCrossEntropy
     if not (isinstance(c0, OhemCrossEntropy) and isinstance(c1, OhemCrossEntropy)):
-        # a CrossEntropyLoss, DiceLoss, FocalLoss or TverskyLoss somewhere: each entry runs on its own (csrc/seg_loss.hip
-        # for those four, the single-loss OHEM kernels for an OhemCrossEntropy next to one of them)
+        # a CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss or LovaszLoss somewhere: each entry runs on its own
+        # (csrc/seg_loss.hip for the first four, csrc/lovasz.hip, the single-loss OHEM kernels for an OhemCrossEntropy
+        # next to one of them)
         losses, outs = [], []
         for crit, logit in ((c0, xc), (c1, xs)):
-            x = fuse_loss_half(logit, h1, h2, hw) if fold else fuse_loss(logit, h1, h2, hw)
+            # a LovaszLoss ranks the full-resolution logits (its kernels have no resize-folded form): that entry alone
+            # leaves the fold, the other one keeps it
+            up = fold and not isinstance(crit, LovaszLoss)
+            x = fuse_loss_half(logit, h1, h2, hw) if up else fuse_loss(logit, h1, h2, hw)
             if isinstance(crit, OhemCrossEntropy):
-                l, out = (OhemUpFn if fold else OhemFn).apply(x, y, crit.thresh, crit.min_kept, crit.loss_weight,
-                                                              crit.ignore_label, crit.class_weight_on(x))
+                l, out = (OhemUpFn if up else OhemFn).apply(x, y, crit.thresh, crit.min_kept, crit.loss_weight,
+                                                            crit.ignore_label, crit.class_weight_on(x))
             else:
                 # the head's ignore_index, as BaseDecodeHead.loss_by_feat passes it (the reference's LEDHead passes
                 # none: its CrossEntropyLoss then runs with -100 and raises on the first padded pixel)
-                l, out = seg_loss_apply(crit, x, y, fold, h.ignore_index)
+                l, out = seg_loss_apply(crit, x, y, up, h.ignore_index)
             losses.append(l)
             outs.append(out)
         return {'loss_context': losses[0], 'loss_spatial': losses[1], 'acc_seg': outs[0][1:2]}
