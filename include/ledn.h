@@ -66,6 +66,9 @@ enum {
                                        0: the generic kernels (A/B measurements); < 0: the default mask */
     LEDN_OPT_BN_FUSED = 4,          /* 1: ledn_bn_act_bwd_fused may launch its persistent one-pass kernel (default 0: it returns
                                        LEDN_ESKIP); see that entry point */
+    LEDN_OPT_DW_BWD_WORKGROUPS = 5, /* persistent workgroups of the fused depthwise 3x3 backward (ledn_dwconv2d_bwd), shared
+                                       out over the 32-channel slices and capped at 256 per slice (default 512: two resident
+                                       per CU) */
     LEDN_OPT_DETERMINISTIC = 3      /* 1: every cross-workgroup reduction of the library (BatchNorm statistics and their
                                        backward sums, weight / bias gradients, pooled contexts and their gradients, the
                                        attention's bias gradient and the gradients of reflect-padded windows) runs in a
@@ -665,6 +668,19 @@ typedef struct {
 } ledn_dwbwd_desc;
 int ledn_dwconv2d_bwd_data(const ledn_dwbwd_desc* d, void* stream);
 int ledn_dwconv2d_bwd_weight(const ledn_dwbwd_desc* d, void* stream);
+/* Both gradients of one descriptor (x, dz, w, dx and dw all set; `add` optional).  When the fused gate holds and
+ * LEDN_OPT_STREAM_FAST bit 1 is set and a workspace of LEDN_OPT_DW_BWD_WORKGROUPS * 9 * 32 floats is bound, ONE kernel
+ * (dw3x3_bwd_tile_kernel, csrc/dwconv.hip) stages dz once in LDS and forms dx and dw from the same taps, followed by the
+ * ordered summing launch of its partial rows; otherwise the call is ledn_dwconv2d_bwd_data followed by
+ * ledn_dwconv2d_bwd_weight.  dx is bit-identical to ledn_dwconv2d_bwd_data's; dw is ADDED into d->dw like
+ * ledn_dwconv2d_bwd_weight's and differs from it only in the order of the f32 sum; no float atomic meets another, so two
+ * calls give the same bits in default and in deterministic mode.
+ * The fused gate (ledn_dwconv2d_bwd_fused_applies: no launch, reads only the shape fields and dtype; 1 = holds):
+ *   dtype bf16; KH = KW = 3; stride 1; ext1 = 0; Ho = H, Wo = W; pad < 0 or pad = dil[g] for every group;
+ *   C % 32 = 0, 256 % (C / 8) = 0, group_size % 8 = 0, C <= 4 * group_size; W >= 32; N * H * W >= 16384;
+ *   N * H * W * C < 2^31; 1 <= dil[g] <= 5; at most 16384 tiles of 16 x 32 (largest dil <= 2) or 8 x 32 pixels. */
+int ledn_dwconv2d_bwd(const ledn_dwbwd_desc* d, void* stream);
+int ledn_dwconv2d_bwd_fused_applies(const ledn_dwbwd_desc* d);
 
 /* SESP pyramid backward.  g = suffix sums of dy over the 4 branch groups
  * (g_b = sum_{b'>=b} dy_b', the adjoint of the HFF adds, eesp.py:84-91):

@@ -19,6 +19,7 @@ F32, BF16, U8 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3, 4
 RES_NONE, RES_ADD, RES_GATE = 0, 1, 2
 OPT_CONV_WORKGROUPS, OPT_WGRAD_WORKGROUPS, OPT_STREAM_FAST, OPT_DETERMINISTIC, OPT_BN_FUSED = 0, 1, 2, 3, 4
+OPT_DW_BWD_WORKGROUPS = 5
 ESKIP = 3
 
 vp, fp, i32, i64 = C.c_void_p, C.c_void_p, C.c_int, C.c_longlong
@@ -198,6 +199,8 @@ _PROTOS = {
     'ledn_bn_act_bwd_fused_check': ([i32, vp], i32),
     'ledn_dwconv2d_bwd_data': ([C.POINTER(DwBwdDesc), vp], i32),
     'ledn_dwconv2d_bwd_weight': ([C.POINTER(DwBwdDesc), vp], i32),
+    'ledn_dwconv2d_bwd': ([C.POINTER(DwBwdDesc), vp], i32),
+    'ledn_dwconv2d_bwd_fused_applies': ([C.POINTER(DwBwdDesc)], i32),
     'ledn_sesp_pyramid_bwd_data': ([C.POINTER(PyrBwdDesc), vp], i32),
     'ledn_sesp_pyramid_bwd_weight': ([C.POINTER(PyrBwdDesc), vp], i32),
     'ledn_sesp_pyramid_bwd_kernel_id': ([C.POINTER(PyrBwdDesc)], i32),

@@ -654,6 +654,19 @@ int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
     return check_launch();
 }
 
+int dw3x3_bwd_fused(const ledn_dwbwd_desc& b, hipStream_t s);   // dwconv.hip; -1 = shape not covered
+
+// both gradients (ledn_dwconv2d_bwd): one fused launch where dw3x3_bwd_tile_kernel applies, else the two above in order
+int dw_bwd_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
+    int rc = dwbwd_validate(d);
+    if (rc != LEDN_OK) return rc;
+    LEDN_REQUIRE(d.x && d.w && d.dx && d.dw);
+    rc = dw3x3_bwd_fused(d, s);
+    if (rc >= 0) return rc;
+    rc = dw_bwd_data_impl(d, s);
+    return rc != LEDN_OK ? rc : dw_bwd_weight_impl(d, s);
+}
+
 // ===========================================================================
 // SESP pyramid backward
 // ===========================================================================

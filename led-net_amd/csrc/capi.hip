@@ -92,6 +92,8 @@ int bn_act_bwd_reduce_impl(const ledn_bnbwd_desc& d, hipStream_t s);
 int bn_act_bwd_apply_impl(const ledn_bnbwd_desc& d, hipStream_t s);
 int dw_bwd_data_impl(const ledn_dwbwd_desc& d, hipStream_t s);
 int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s);
+int dw_bwd_impl(const ledn_dwbwd_desc& d, hipStream_t s);
+bool dw3x3_bwd_fused_applies(const ledn_dwbwd_desc& b);
 int pyr_bwd_data_impl(const ledn_pyrbwd_desc& d, hipStream_t s);
 int pyr_bwd_weight_impl(const ledn_pyrbwd_desc& d, hipStream_t s);
 int pyr_bwd_data_kernel_id(const ledn_pyrbwd_desc& d);
@@ -183,7 +185,7 @@ static hipStream_t enter_stream(void* stream) {         // every extern "C" entr
     return (hipStream_t)stream;
 }
 Workspace& workspace() { return tls_ws; }
-static Options g_opt = {512, 512, 91, 0, 0};   // stream_fast: bit 0 BatchNorm / affine streaming kernels, bit 1 LDS-tiled depthwise 3x3, bit 2 round-robin conv tiles (off), bit 3 8-row conv tiles for under-filled grids, bit 4 register-direct 1x1 conv (conv1x1.hip), bit 5 resident 3x3 weights for 32 < Cin <= 64 (off: measured slower, r3l), bit 6 register-direct 3x3 conv for 32 input channels (conv3x3.hip)
+static Options g_opt = {512, 512, 91, 0, 0, 512};   // stream_fast: bit 0 BatchNorm / affine streaming kernels, bit 1 LDS-tiled depthwise 3x3, bit 2 round-robin conv tiles (off), bit 3 8-row conv tiles for under-filled grids, bit 4 register-direct 1x1 conv (conv1x1.hip), bit 5 resident 3x3 weights for 32 < Cin <= 64 (off: measured slower, r3l), bit 6 register-direct 3x3 conv for 32 input channels (conv3x3.hip)
 Options& options() { return g_opt; }
 static thread_local DeferredStats g_defer = {false, nullptr, 0};
 DeferredStats& deferred_stats() { return g_defer; }
@@ -221,6 +223,7 @@ int ledn_set_option(int option, long long value) {
         case LEDN_OPT_STREAM_FAST: options().stream_fast = value < 0 ? 91 : (int)value; return LEDN_OK;   // (< 0: the default mask)
         case LEDN_OPT_DETERMINISTIC: options().deterministic = value > 0 ? 1 : 0; return LEDN_OK;
         case LEDN_OPT_BN_FUSED: options().bn_fused = value > 0 ? 1 : 0; return LEDN_OK;
+        case LEDN_OPT_DW_BWD_WORKGROUPS: options().dw_bwd_workgroups = value > 0 ? (int)value : 512; return LEDN_OK;
         default: return LEDN_EINVAL;
     }
 }
@@ -513,6 +516,8 @@ int ledn_dwconv2d_bwd_data(const ledn_dwbwd_desc* d, void* stream) {
 int ledn_dwconv2d_bwd_weight(const ledn_dwbwd_desc* d, void* stream) {
     return d ? dw_bwd_weight_impl(*d, S(stream)) : LEDN_EINVAL;
 }
+int ledn_dwconv2d_bwd(const ledn_dwbwd_desc* d, void* stream) { return d ? dw_bwd_impl(*d, S(stream)) : LEDN_EINVAL; }
+int ledn_dwconv2d_bwd_fused_applies(const ledn_dwbwd_desc* d) { return d && dw3x3_bwd_fused_applies(*d) ? 1 : 0; }
 int ledn_sesp_pyramid_bwd_data(const ledn_pyrbwd_desc* d, void* stream) {
     return d ? pyr_bwd_data_impl(*d, S(stream)) : LEDN_EINVAL;
 }

@@ -751,6 +751,171 @@ int dw3x3_bwd_data_bf16(const ledn_dwbwd_desc& b, hipStream_t s) {   // used by 
 int finish_partials(const float* part, int nblk, int C, int nout, float* o0, float* o1, float* o2,
                     hipStream_t s);
 
+// Data AND weight gradient of the same convolution in one pass (ledn_dwconv2d_bwd).  The data gradient above reads the nine
+// taps dz[q + tap_t] of its pixel q from the LDS patch; these are also every dz value that x[q] meets in the weight gradient:
+//   dw[t'][c] = sum_p x[p + tap_t'][c] * dz[p][c] = sum_q x[q][c] * dz[q - tap_t'][c],   q - tap_t' = q + tap_(8 - t')
+// (dz outside the image is the patch's zero fill, exactly the terms the zero padding of x drops).  So the lane loads its own
+// x pixel once, 16 bytes and no halo, and every unpacked tap feeds two packed FMAs: dx in dw3x3_tile_kernel<1>'s order (bit-
+// identical) and the 9 x 8 weight-gradient sums, which stay in registers.  x is read 1.0 x instead of nine times through the
+// vector L1, dz once instead of twice, and there is one LDS patch as before (46 / 48 KB: two workgroups per CU).
+// Workgroups are persistent: workgroup (row, slice) walks tiles row, row + R, .. of its 32-channel slice and leaves ONE
+// partial row [9][32]; the epilogue is a reduce-scatter over the wave's four 16-lane rows (v_permlane32_swap,
+// v_permlane16_swap: 72 -> 18 values per lane), two DPP steps over the row's four pixel lanes and the four waves through
+// LDS.  finish_partials adds the R <= 256 rows into dw with one adder per element: no float atomic meets another.
+template <int HL, int TH>
+__global__ void __launch_bounds__(256, 2) dw3x3_bwd_tile_kernel(ledn_dwbwd_desc d, float* part, int R) {
+    constexpr int TW = 32, PW = TW + 2 * HL, PH = TH + 2 * HL, CW = 32, PXB = CW * 2;
+    constexpr int NL = (PH * PW * 4 + 255) / 256;
+    __shared__ __attribute__((aligned(16))) unsigned char s_patch[PH * PW * PXB];
+    static_assert(PH * PW * PXB >= 4 * 9 * CW * 4, "the weight-gradient exchange reuses the patch");
+    float* s_red = reinterpret_cast<float*>(s_patch);     // [4 waves][9][32]
+    const int tid = threadIdx.x;
+    const int tx = (d.W + TW - 1) / TW, ty = (d.H + TH - 1) / TH, nch = d.C / CW;
+    const int tiles = d.N * tx * ty;
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);
+    const int ch = (int)(bid % (unsigned)nch), row = (int)(bid / (unsigned)nch);
+    const int cg = tid & 3, pl = tid >> 2;
+    const int c = ch * CW + cg * 8;
+    const int dl = d.dil[c / d.group_size];
+    f32x2_t w[9][4], acc[9][4];     // acc[t] = the sums of filter tap 8 - t
+    int toff[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        f32x8_load(d.w + (long)(8 - t) * d.C + c, w[t]);
+        toff[t] = (((t / 3 - 1) * dl) * PW + (t % 3 - 1) * dl) * PXB;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[t][i] = f32x2_t{0.f, 0.f};
+    }
+    const int lx = pl & 31;
+    for (int tile = row; tile < tiles; tile += R) {
+        const int txi = tile % tx, tyi = (tile / tx) % ty, n = tile / (tx * ty);
+        const int y0 = tyi * TH - HL, x0 = txi * TW - HL;
+        const long img = (long)n * d.H * d.W * d.C;
+        const bf16_t* zin = reinterpret_cast<const bf16_t*>(d.dz) + img + ch * CW;
+        const bf16_t* xin = reinterpret_cast<const bf16_t*>(d.x) + img + c;
+        bf16_t* y = reinterpret_cast<bf16_t*>(d.dx) + img + c;
+        const bf16_t* addp = d.add ? reinterpret_cast<const bf16_t*>(d.add) + img + c : nullptr;
+        const int gx = txi * TW + lx;
+        // the lane's own x (and add) pixel of a pass is requested two passes ahead (the first two together with the patch):
+        // with two waves per SIMD nothing else would cover the latency of that load
+        const int gy0 = tyi * TH + (pl >> 5);
+        auto request = [&](int pass, uint4& xr, uint4& ar) {
+            const int gy = gy0 + pass * 2;
+            if (pass < TH / 2 && gy < d.H && gx < d.W) {
+                const unsigned o = (unsigned)((gy * d.W + gx) * d.C);
+                xr = *reinterpret_cast<const uint4*>(xin + o);
+                if (addp) ar = *reinterpret_cast<const uint4*>(addp + o);
+            }
+        };
+        uint4 xa = {0u, 0u, 0u, 0u}, xb = xa, aa = xa, ab = xa;      // aa, ab stay zero without `add`: dx starts from +0
+        request(0, xa, aa);
+        request(1, xb, ab);
+        {
+            const int tid_o = opaque(tid);      // the patch coordinates of the NL loads are not to be kept across tiles
+            uint4 stage[NL];
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+                const int e = tid_o + i * 256, px = e >> 2, q = e & 3;
+                const int gy = y0 + px / PW, gx = x0 + px % PW;
+                const bool ok = e < PH * PW * 4 && gy >= 0 && gy < d.H && gx >= 0 && gx < d.W;
+                const unsigned off = ok ? (unsigned)((gy * d.W + gx) * d.C + q * 8) : 0u;      // < 2^31 elements (the gate)
+                const uint4 v = *reinterpret_cast<const uint4*>(zin + off);
+                stage[i] = ok ? v : uint4{0u, 0u, 0u, 0u};
+            }
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+                const int e = tid_o + i * 256;
+                if (e < PH * PW * 4) *reinterpret_cast<uint4*>(s_patch + (long)e * 16) = stage[i];
+            }
+        }
+        __syncthreads();
+        auto do_pass = [&](int pass, uint4& xr, uint4& ar) {
+            const int ly = pass * 2 + (pl >> 5), gy = gy0 + pass * 2;
+            f32x2_t dxv[4], xc[4];
+            bf16x8_unpack(ar, dxv);
+            bf16x8_unpack(xr, xc);
+            request(pass + 2, xr, ar);
+            if (gy >= d.H || gx >= d.W) return;
+            const unsigned o = (unsigned)((gy * d.W + gx) * d.C);
+            const unsigned char* ctr = s_patch + ((ly + HL) * PW + lx + HL) * PXB + cg * 16;
+            uint4 raw[9];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) raw[t] = *reinterpret_cast<const uint4*>(ctr + toff[t]);
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                f32x2_t zv[4];
+                bf16x8_unpack(raw[t], zv);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    dxv[i] = pk_fma(zv[i], w[t][i], dxv[i]);
+                    acc[t][i] = pk_fma(zv[i], xc[i], acc[t][i]);
+                }
+            }
+            *reinterpret_cast<uint4*>(y + o) = bf16x8_pack(dxv);
+        };
+#pragma unroll 1
+        for (int pass = 0; pass < TH / 2; pass += 2) {
+            do_pass(pass, xa, aa);
+            do_pass(pass + 1, xb, ab);
+        }
+        __syncthreads();      // the next tile's staging (or the exchange below) overwrites the patch
+    }
+    // wave: rows of 16 lanes = 4 pixel lanes x 4 channel groups.  After the two swaps the lane of row rr holds, per tap, the
+    // pair i = 2 * (rr & 1) + (rr >> 1) of its 8 channels summed over the four rows; row_ror 4 and 8 sum the pixel lanes
+    f32x2_t s[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        swap_add32(acc[t][0], acc[t][1]);
+        swap_add32(acc[t][2], acc[t][3]);
+        swap_add16(acc[t][0], acc[t][2]);
+        s[t].x = lane_step_sum(lane_step_sum(acc[t][0].x, 4), 8);
+        s[t].y = lane_step_sum(lane_step_sum(acc[t][0].y, 4), 8);
+    }
+    const int lane = tid & 63, wid = tid >> 6, rr = lane >> 4;
+    if ((lane & 15) < 4) {
+        const int cc = cg * 8 + 2 * (2 * (rr & 1) + (rr >> 1));
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+            *reinterpret_cast<float2*>(s_red + (wid * 9 + 8 - t) * CW + cc) = make_float2(s[t].x, s[t].y);
+    }
+    __syncthreads();
+    for (int e = tid; e < 9 * CW; e += 256) {
+        const float sum = (s_red[e] + s_red[9 * CW + e]) + (s_red[18 * CW + e] + s_red[27 * CW + e]);
+        part[(long)row * 9 * d.C + (long)(e / CW) * d.C + ch * CW + e % CW] = sum;
+    }
+}
+
+// the fused kernel's shape class (ledn.h: ledn_dwconv2d_bwd_fused_applies): dw3x3_tile_launch's, read from the shape fields
+bool dw3x3_bwd_fused_applies(const ledn_dwbwd_desc& b) {
+    if (b.dtype != LEDN_BF16 || b.Ho != b.H || b.Wo != b.W || b.C <= 0 || b.group_size <= 0 || b.C > 4 * b.group_size ||
+        !dw3x3_bf16_ok(b.C, b.group_size, b.KH, b.KW, b.stride, b.pad, b.ext1, b.dil, (long)b.N * b.H * b.W * b.C))
+        return false;
+    if (b.C % 32 || b.W < 32 || (long)b.N * b.H * b.W < 16384) return false;
+    int hl = 0;
+    for (int g = 0; g * b.group_size < b.C; ++g) {
+        if (b.dil[g] < 1) return false;
+        hl = b.dil[g] > hl ? b.dil[g] : hl;
+    }
+    if (hl > 5) return false;
+    return (long)b.N * cdiv(b.H, hl <= 2 ? 16 : 8) * cdiv(b.W, 32) <= 16384;
+}
+
+int dw3x3_bwd_fused(const ledn_dwbwd_desc& b, hipStream_t s) {   // used by backward.hip; -1 = not covered (or no workspace)
+    if (!(options().stream_fast & 2) || !dw3x3_bwd_fused_applies(b)) return -1;
+    int hl = 0;
+    for (int g = 0; g * b.group_size < b.C; ++g) hl = b.dil[g] > hl ? b.dil[g] : hl;
+    const int nch = b.C / 32;
+    // R partial rows = workgroups per slice: at most 256, so that finish_partials runs unsplit (one adder per element).
+    // A workgroup whose row has no tile (R > tiles) writes a row of zeros
+    long R = options().dw_bwd_workgroups / nch;
+    R = R < 1 ? 1 : R > 256 ? 256 : R;
+    float* part = ws_take(R * 9 * b.C);
+    if (!part) return -1;
+    if (hl <= 2) LEDN_LAUNCH((dw3x3_bwd_tile_kernel<2, 16>), dim3((unsigned)(R * nch)), dim3(256), 0, s, b, part, (int)R);
+    else LEDN_LAUNCH((dw3x3_bwd_tile_kernel<5, 8>), dim3((unsigned)(R * nch)), dim3(256), 0, s, b, part, (int)R);
+    return finish_partials(part, (int)R, 9 * b.C, 1, b.dw, nullptr, nullptr, s);
+}
+
 int dwconv_impl(const ledn_dw_desc& d, hipStream_t s) {
     LEDN_REQUIRE(d.x && d.w && d.y);
     LEDN_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.C > 0 && d.Ho > 0 && d.Wo > 0);

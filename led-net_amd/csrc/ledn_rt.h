@@ -418,6 +418,7 @@ struct Options {
     int stream_fast;
     int deterministic;      // LEDN_OPT_DETERMINISTIC: every cross-workgroup reduction in a fixed order (no f32 atomics)
     int bn_fused;           // LEDN_OPT_BN_FUSED: the persistent one-pass BatchNorm backward may be launched
+    int dw_bwd_workgroups;  // LEDN_OPT_DW_BWD_WORKGROUPS: workgroups of the fused depthwise 3x3 backward (dwconv.hip)
 };
 Options& options();
 // A/B measurement knobs (getenv) are honoured only in experimental mode (LEDN_EXPERIMENTAL=1): an old shell export must

@@ -257,6 +257,13 @@ def _dw_desc(x_shape, dz, w_khwc, stride, pad, dil, group_size, ext1, dtype):
     return d
 
 
+def dwconv2d_bwd_fused_applies(x, dz, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_size=None, ext1=False):
+    """ledn_dwconv2d_bwd_fused_applies for these operands (no launch): dwconv2d_bwd with both gradients wanted runs
+    dw3x3_bwd_tile_kernel on them"""
+    d = _dw_desc(x.shape, dz, w_khwc, stride, pad, dil, group_size, ext1, _dt(x))
+    return bool(_lib.get_lib().cdll.ledn_dwconv2d_bwd_fused_applies(d))
+
+
 def dwconv2d_bwd(x, dz, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_size=None, ext1=False,
                  add=None, need_dx=True, need_dw=True, dw_out=None):
     """-> (dx or None, dw [KH,KW,C] or None)."""
@@ -268,6 +275,23 @@ def dwconv2d_bwd(x, dz, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_siz
     _check(lib, x, dz, w_khwc, add)
     d.x, d.dz, d.w, d.add = _p(x), _p(dz), _p(_f32(w_khwc)), _p(add)
     KH, KW, Cc = w_khwc.shape
+    side = DW_WGRAD_SLOT and _ops.MULTI_STREAM and x.is_cuda and dw_out is not None and _ops._slot(x) == 0
+    if need_dx and need_dw and not side:
+        # both gradients on one stream: ledn_dwconv2d_bwd (one fused launch on dw3x3_bwd_tile_kernel's shape class,
+        # include/ledn.h; else the two calls below, made by the library)
+        dx = torch.empty_like(x)
+        dw = dw_out if dw_out is not None else _ops.zeros_f32(tuple(w_khwc.shape), x.device)
+        if tuple(dw.shape) != tuple(w_khwc.shape) or dw.dtype != torch.float32:
+            raise LednError('dwconv2d_bwd: dw_out shape/dtype mismatch')
+        _check(lib, dw)
+        d.dx, d.dw = _p(dx), _p(dw)
+        work = None
+        if _ops._TIMING is not None:
+            work = (f'dwbwd{KH}x{KW} C{Cc} {tuple(x.shape)}', _nb(x, dz, dx, add), 4 * dz.numel() * KH * KW)
+            if lib.cdll.ledn_dwconv2d_bwd_fused_applies(d):
+                work += ('dw3x3_bwd_tile_kernel',)
+        _run(lib, 'ledn_dwconv2d_bwd', x, d, work=work)
+        return dx, dw
     if need_dx:
         dx = torch.empty_like(x)
         d.dx = _p(dx)

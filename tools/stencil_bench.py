@@ -2,8 +2,9 @@
 gradient, weight gradient, each launch timed with HIP events (ops.start_timing) over rotating buffer sets whose total
 exceeds the 256 MB Infinity Cache, so that every call streams from HBM as it does inside the step.
 Pyramid cases carry a stride; the context-branch blocks' shapes (dilations [1,2,3,4], stride 1 and 2 at 1/8, 1/16 and 1/32
-resolution) and the adjoint of their 3x3/s2 average-pool shortcut (with its addend) are included.
-    python tools/stencil_bench.py [--iters 24] [--only pyr|dw|avg]"""
+resolution) and the adjoint of their 3x3/s2 average-pool shortcut (with its addend) are included.  The dw cases time what
+ops_train.dwconv2d_bwd launches: one fused call (dwconv2d_bwd) where dw3x3_bwd_tile_kernel applies, else data + weight.
+    python tools/stencil_bench.py [--iters 24] [--only pyr|dw|avg] [--dw-bwd-wgs N]"""
 import argparse
 import os
 import sys
@@ -16,10 +17,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=24)
     ap.add_argument('--only', default=None, help='run only the cases of this kind (pyr, dw, avg)')
+    ap.add_argument('--dw-bwd-wgs', type=int, default=0, help='LEDN_OPT_DW_BWD_WORKGROUPS (0 = default)')
     args = ap.parse_args()
     import importlib
     importlib.import_module('led_net_amd')
-    from led_net_amd import ops, ops_train as T
+    from led_net_amd import _lib, ops, ops_train as T
+    if args.dw_bwd_wgs:
+        _lib.get_lib().set_option(_lib.OPT_DW_BWD_WORKGROUPS, args.dw_bwd_wgs)
     dev = torch.device('cuda:0')
     g = torch.Generator(device='cpu').manual_seed(1)
     bf = torch.bfloat16
@@ -34,6 +38,10 @@ def main():
              ('pyr', 16, 32, 32, 128, ctx, 1), ('pyr', 16, 32, 32, 128, ctx, 2),
              ('dw', 16, 128, 128, 64, [2, 2, 2, 2], 16), ('dw', 16, 128, 128, 128, [2, 2, 2, 2], 32),
              ('dw', 16, 128, 128, 128, [2, 3, 4, 5], 32), ('dw', 16, 64, 64, 256, [2, 3, 4, 5], 64),
+             # the context branch's other second-stage depthwise convs (LEDN_BENCH_VERBOSE table of the step): behind the
+             # stride-2 pyramids at 1/16 and 1/32 resolution, and the 1/32 stride-1 blocks
+             ('dw', 16, 64, 64, 128, [2, 3, 4, 5], 32), ('dw', 16, 32, 32, 256, [2, 3, 4, 5], 64),
+             ('dw', 16, 32, 32, 512, [2, 3, 4, 5], 128),
              ('avg', 16, 128, 128, 128, None, 0), ('avg', 16, 64, 64, 256, None, 0), ('avg', 16, 32, 32, 512, None, 0)]
     for kind, N, H, W, n, dil, gs in cases:
         if args.only and kind != args.only:
