@@ -966,6 +966,32 @@ int ledn_lovasz_loss_bwd(const float* work, const float* out, const float* dloss
                          float* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The exact squared Euclidean distance transform, and HuasdorffDisstanceLoss (the reference's spelling;
+ * mmseg/models/losses/huasdorff_distance_loss.py:14-156) on top of it (csrc/hausdorff.hip).
+ * ledn_edt_sq: mask uint8 [N][H][W] (non-zero = foreground) -> out int32 [N][H][W]: for a foreground pixel the squared
+ * distance to the nearest background pixel of its image, 0 on background; exact integers (a column pass and a row pass,
+ * no square root).  An image WITHOUT a background pixel gets (y + 1)^2 + x^2, what scipy's distance_transform_edt
+ * returns for such a mask (the distance to a ghost pixel at row -1, column 0).
+ * The loss, on NHWC f32 logits [N][H][W][C] and int64 labels [N][H][W]: p = softmax(logits), y = the label with
+ * ignore_index set to 0 (those pixels stay in the mean, as background with target 0), M_gt = (y != 0), M_seg =
+ * (argmax != 0) with the first maximum of the f32 logits, D = edt_sq(M_seg) + edt_sq(M_gt), and
+ * out[0] = loss_weight / (C N H W) * sum_pixels D * sum_{i=1..C-1} (p_i - y)^2, y the raw label value as a float.
+ * out[4]: loss, top-1 accuracy in percent over the pixels with label != acc_ignore_index (as the CE / Dice entry
+ * points), the divisor C N H W, the number of those pixels.  The sum is formed in f64 from per-workgroup partials in a
+ * fixed order: no atomics, no waiting between workgroups, bit-reproducible, hipGraph-capturable.
+ * work: ledn_hausdorff_work_bytes(N, H, W, C) bytes, 16-byte aligned (0 for sizes outside the limits): hdr[4] (f32
+ * loss_weight, f32 loss_weight / (C N H W), int32 ignore_index, -), D as int32 [N*H*W] from byte 16, the second map
+ * and the partials.  The backward, from the logits, the labels and work: dlogits_k = dloss[0] * loss_weight / (C N H W)
+ * * D * p_k * (a_k - sum_i a_i p_i), a_0 = 0, a_i = 2 (p_i - y).
+ * Limits: W <= 8192, H^2 + W^2 < 2^30, N <= 65535, N*H*W < 2^31; the loss: 2 <= C <= 32. */
+int ledn_edt_sq(const unsigned char* mask, int N, int H, int W, int* out, void* stream);
+long long ledn_hausdorff_work_bytes(long long N, long long H, long long W, int C);
+int ledn_hausdorff_loss_fwd(const float* logits, const long long* target, int N, int H, int W, int C, int ignore_index,
+                            int acc_ignore_index, float loss_weight, float* work, float* out, void* stream);
+int ledn_hausdorff_loss_bwd(const float* logits, const long long* target, int N, int H, int W, int C, const float* work,
+                            const float* dloss, float* dlogits, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The four pooled-context MLPs of Muti_AFF (classification/model_utils.py:377-400: AdaptiveAvgPool2d(S) ->
  * Conv1x1(C->Ci)+bias -> BatchNorm -> ReLU -> Conv1x1(Ci->C)+bias -> [BatchNorm: in the gate kernel], S = 4, 8, 16, 1)
  * as ONE launch sequence for all four scales: they are chains of tiny launch-bound kernels (~50 launches per

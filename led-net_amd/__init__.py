@@ -2,7 +2,7 @@
 
 Public surface = the reference's plugin names:
 ``MODELS.build(dict(type='LEDNet'|'LEDHead'|'OhemCrossEntropy'|'CrossEntropyLoss'|'DiceLoss'|'FocalLoss'|
-'TverskyLoss'|'LovaszLoss'|'EncoderDecoder'|'SegTTAModel', ...))``.
+'TverskyLoss'|'LovaszLoss'|'HuasdorffDisstanceLoss'|'EncoderDecoder'|'SegTTAModel', ...))``.
 Compute is in csrc/libledn_hip.so (C ABI: include/ledn.h); there is no CPU path.
 """
 from . import _lib, ops  # noqa: F401
@@ -10,7 +10,8 @@ from ._lib import is_deterministic, set_deterministic  # noqa: F401
 from .registry import BACKBONES, HEADS, LOSSES, MODELS, SEGMENTORS, register_into_mmseg  # noqa: F401
 from .lednet import LEDNet
 from .led_head import LEDHead
-from .losses import CrossEntropyLoss, DiceLoss, FocalLoss, LovaszLoss, OhemCrossEntropy, TverskyLoss  # noqa: F401
+from .losses import (CrossEntropyLoss, DiceLoss, FocalLoss, HuasdorffDisstanceLoss, LovaszLoss,  # noqa: F401
+                     OhemCrossEntropy, TverskyLoss)
 from .segmentor import EncoderDecoder, SegDataPreProcessor, SegDataSample, SegTTAModel  # noqa: F401
 from .config import load_config  # noqa: F401
 from .train import Trainer  # noqa: F401
@@ -22,5 +23,5 @@ MODELS.register_module(module=LEDNet)
 MODELS.register_module(module=LEDHead)
 
 __all__ = ['MODELS', 'LEDNet', 'LEDHead', 'OhemCrossEntropy', 'CrossEntropyLoss', 'DiceLoss', 'FocalLoss',
-           'TverskyLoss', 'LovaszLoss', 'EncoderDecoder', 'SegTTAModel', 'SegDataSample',
+           'TverskyLoss', 'LovaszLoss', 'HuasdorffDisstanceLoss', 'EncoderDecoder', 'SegTTAModel', 'SegDataSample',
            'load_config', 'ops', 'register_into_mmseg', 'Trainer']

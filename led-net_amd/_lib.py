@@ -254,6 +254,11 @@ _PROTOS = {
     'ledn_lovasz_work_bytes': ([i64, i64, i32, i32], i64),
     'ledn_lovasz_loss_fwd': ([fp, vp, i32, i64, i32, fp, vp, i32, i32, i32, i32, i32, C.c_float, fp, fp, vp], i32),
     'ledn_lovasz_loss_bwd': ([fp, fp, fp, i32, i64, i32, fp, vp], i32),
+    # HuasdorffDisstanceLoss and the distance transform under it (hausdorff.hip)
+    'ledn_edt_sq': ([vp, i32, i32, i32, vp, vp], i32),
+    'ledn_hausdorff_work_bytes': ([i64, i64, i64, i32], i64),
+    'ledn_hausdorff_loss_fwd': ([fp, vp, i32, i32, i32, i32, i32, i32, C.c_float, fp, fp, vp], i32),
+    'ledn_hausdorff_loss_bwd': ([fp, vp, i32, i32, i32, i32, fp, fp, fp, vp], i32),
     'ledn_sgd_step': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, vp], i32),
     'ledn_grad_norm_partials': ([fp, i64, i32, fp, i32, vp], i32),
     'ledn_sgd_step_clip': ([vp, i32, i64, C.c_float, fp, C.c_float, C.c_float, C.c_float, fp, i32, i32, C.c_float, C.c_float,

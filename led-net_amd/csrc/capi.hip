@@ -147,6 +147,12 @@ int lovasz_fwd_impl(const float* logits, const long long* target, int N, long lo
                     float loss_weight, float* work, float* out, hipStream_t s);
 int lovasz_bwd_impl(const float* work, const float* out, const float* dloss, int N, long long HW, int C, float* dlogits,
                     hipStream_t s);
+int edt_sq_impl(const unsigned char* mask, int N, int H, int W, int* out, hipStream_t s);
+long long hausdorff_work_bytes(long long N, long long H, long long W, int C);
+int hausdorff_fwd_impl(const float* logits, const long long* target, int N, int H, int W, int C, int ignore_index,
+                       int acc_ignore_index, float loss_weight, float* work, float* out, hipStream_t s);
+int hausdorff_bwd_impl(const float* logits, const long long* target, int N, int H, int W, int C, const float* work,
+                       const float* dloss, float* dlogits, hipStream_t s);
 int tta_accumulate_impl(const ledn_tta_desc& d, hipStream_t s);
 int slide_accumulate_impl(float* canvas, const float* crop, int N, int C, int H, int W, int y1, int x1, int hc, int wc,
                           int crop_planar, hipStream_t s);
@@ -763,6 +769,21 @@ int ledn_lovasz_loss_fwd(const float* logits, const long long* target, int N, lo
 int ledn_lovasz_loss_bwd(const float* work, const float* out, const float* dloss, int N, long long HW, int C,
                          float* dlogits, void* stream) {
     return lovasz_bwd_impl(work, out, dloss, N, HW, C, dlogits, S(stream));
+}
+int ledn_edt_sq(const unsigned char* mask, int N, int H, int W, int* out, void* stream) {
+    return edt_sq_impl(mask, N, H, W, out, S(stream));
+}
+long long ledn_hausdorff_work_bytes(long long N, long long H, long long W, int C) {
+    return hausdorff_work_bytes(N, H, W, C);
+}
+int ledn_hausdorff_loss_fwd(const float* logits, const long long* target, int N, int H, int W, int C, int ignore_index,
+                            int acc_ignore_index, float loss_weight, float* work, float* out, void* stream) {
+    return hausdorff_fwd_impl(logits, target, N, H, W, C, ignore_index, acc_ignore_index, loss_weight, work, out,
+                              S(stream));
+}
+int ledn_hausdorff_loss_bwd(const float* logits, const long long* target, int N, int H, int W, int C, const float* work,
+                            const float* dloss, float* dlogits, void* stream) {
+    return hausdorff_bwd_impl(logits, target, N, H, W, C, work, dloss, dlogits, S(stream));
 }
 int ledn_sgd_step(const ledn_sgd_entry* table_dev, int n_tensors, long long max_n, float lr,
                   const float* lr_dev, float momentum, float weight_decay, float grad_scale, void* stream) {

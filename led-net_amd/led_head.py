@@ -54,11 +54,14 @@ class LEDHead(Block):
         if isinstance(loss_decode, dict):
             loss_decode = [loss_decode]
         self.loss_decode = nn.ModuleList(build_loss(c) for c in loss_decode)
-        from .losses import CrossEntropyLoss, DiceLoss, FocalLoss, LovaszLoss, OhemCrossEntropy, TverskyLoss
+        from .losses import (CrossEntropyLoss, DiceLoss, FocalLoss, HuasdorffDisstanceLoss, LovaszLoss, OhemCrossEntropy,
+                             TverskyLoss)
         for i, crit in enumerate(self.loss_decode):
-            if not isinstance(crit, (OhemCrossEntropy, CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss, LovaszLoss)):
-                raise TypeError(f'LEDHead: loss_decode[{i}] is a {type(crit).__name__}; supported: OhemCrossEntropy, '
-                                f'CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss, LovaszLoss')
+            if not isinstance(crit, (OhemCrossEntropy, CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss, LovaszLoss,
+                                     HuasdorffDisstanceLoss)):
+                raise TypeError(f'LEDHead: loss_decode[{i}] is a {type(crit).__name__}; supported: '
+                                f'HuasdorffDisstanceLoss, OhemCrossEntropy, CrossEntropyLoss, DiceLoss, FocalLoss, '
+                                f'TverskyLoss, LovaszLoss')
         self.init_weights()
 
     @staticmethod
@@ -128,7 +131,8 @@ class LEDHead(Block):
     def loss_by_feat(self, seg_logits, batch_data_samples):
         """led_head.py:101-146: (context, spatial, head_x1, head_x2) logits (NCHW, as ``forward`` returns them in
         training) -> the two fused pyramids at the label size, loss_decode[0] / [1] on them (OhemCrossEntropy,
-        CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss or LovaszLoss, each called with the head's ignore_index) and the top-1
+        CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss, LovaszLoss or HuasdorffDisstanceLoss, each called with the head's
+        ignore_index) and the top-1
         accuracy of the context logits; keys ``loss_context``, ``loss_spatial``, ``acc_seg``."""
         from .train import led_head_loss_by_feat
         return led_head_loss_by_feat(self, seg_logits, batch_data_samples)

@@ -1,4 +1,5 @@
-"""OhemCrossEntropy, CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss and LovaszLoss (registered under the reference's names)
+"""OhemCrossEntropy, CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss, LovaszLoss and HuasdorffDisstanceLoss (registered
+under the reference's names)
 and accuracy.
 
 Mirrors mmseg/models/losses/ohem_cross_entropy_loss.py:11-94 (constructor
@@ -19,6 +20,9 @@ same way, on further kernels of csrc/seg_loss.hip; DESIGN.md "FocalLoss and Tver
 
 LovaszLoss (the multi-class Lovasz-Softmax form) mirrors losses/lovasz_loss.py:225-323; its arithmetic is the on-device
 radix sort and closed-form Lovasz gradient of csrc/lovasz.hip; DESIGN.md "LovaszLoss in the head".
+
+HuasdorffDisstanceLoss mirrors losses/huasdorff_distance_loss.py:77-160 on the exact on-device distance transform of
+csrc/hausdorff.hip; DESIGN.md "HuasdorffDisstanceLoss in the head".
 """
 import math
 
@@ -337,6 +341,58 @@ class LovaszLoss(_ClassWeighted):
         """cls_score: N x C x H x W (any float layout), label: N x H x W int64."""
         from .train import seg_loss
         return seg_loss(self, cls_score, label, ignore_index)
+
+    @property
+    def loss_name(self):
+        return self._loss_name
+
+
+@MODELS.register_module()
+class HuasdorffDisstanceLoss(nn.Module):
+    """losses/huasdorff_distance_loss.py:77-160 (the reference's spelling, so that its configs load).  The loss's own
+    ``ignore_index`` is the constructor's: the reference swallows a call-time ``ignore_index`` in ``**kwargs``; those
+    pixels become background with target 0 and stay in the mean.  'mean', 'sum' and 'none' give the same scalar (the
+    reference reduces a scalar).  ``class_weight`` is rejected: the reference's own check of it
+    (``class_weight.ndim == num_class``) fails for every weight vector."""
+
+    def __init__(self, reduction='mean', class_weight=None, loss_weight=1.0, ignore_index=255,
+                 loss_name='loss_huasdorff_disstance', **kwargs):
+        super().__init__()
+        if isinstance(class_weight, str):
+            raise TypeError(f'HuasdorffDisstanceLoss: class_weight={class_weight!r}: a file path is not supported')
+        if class_weight is not None:
+            raise NotImplementedError('HuasdorffDisstanceLoss: class_weight is not supported (the reference asserts '
+                                      'class_weight.ndim == num_class, which no weight vector passes)')
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError(f"HuasdorffDisstanceLoss: reduction={reduction!r} must be 'none', 'mean' or 'sum'")
+        self.reduction = reduction
+        self.class_weight = None
+        self.loss_weight = loss_weight
+        self.ignore_index = 255 if ignore_index is None else int(ignore_index)
+        self._loss_name = loss_name
+
+    def extra_repr(self):
+        return f'reduction={self.reduction!r}, ignore_index={self.ignore_index}, loss_weight={self.loss_weight}'
+
+    def kernel_args(self, logits, ignore_index):
+        """(family, keyword arguments of ops_train.hausdorff_loss_fwd, of hausdorff_loss_bwd) for channels-last
+        `logits`; ignore_index: the head's, which the accuracy uses -- the loss uses the constructor's"""
+        Cc = logits.shape[-1]
+        if 1 <= self.ignore_index < Cc:
+            raise ValueError(f'{self.loss_name}: ignore_index={self.ignore_index} is one of the {Cc} classes of the loss '
+                             f'(the reference then repeats the previous class\'s term by accident)')
+        return 'hausdorff', dict(loss_weight=self.loss_weight, ignore_index=self.ignore_index,
+                                 acc_ignore_index=ignore_index), {}
+
+    def forward(self, pred, target, ignore_index=255, **kwargs):
+        """pred: N x C x H x W (any float layout), target: N x H x W int64.  ``ignore_index`` here is what the accuracy
+        leaves out (the loss keeps the constructor's); ``avg_factor`` is not supported."""
+        if kwargs.get('avg_factor') is not None:
+            raise NotImplementedError(f'{self.loss_name}: avg_factor is not supported')
+        if kwargs.get('reduction_override') not in (None, 'none', 'mean', 'sum'):
+            raise ValueError(f"{self.loss_name}: reduction_override={kwargs['reduction_override']!r}")
+        from .train import seg_loss
+        return seg_loss(self, pred, target, ignore_index)
 
     @property
     def loss_name(self):

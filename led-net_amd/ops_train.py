@@ -1034,6 +1034,84 @@ def lovasz_loss_bwd(logits, target, work, out, dloss):
     return dl
 
 
+# --------------------------------------------------------------------------- #
+# HuasdorffDisstanceLoss (csrc/hausdorff.hip): an exact squared distance transform of the label and argmax masks on the
+# device and the distance-weighted squared probability error on top of it
+# --------------------------------------------------------------------------- #
+HAUSDORFF_MAX_WIDTH = 8192        # one row of the transform sits in LDS (csrc/hausdorff.hip HD_MAX_W)
+HAUSDORFF_MAX_CLASSES = 32
+
+
+def _edt_shape(who, N, H, W):
+    if W > HAUSDORFF_MAX_WIDTH:
+        raise LednError(f'{who}: width {W}; the distance transform takes at most {HAUSDORFF_MAX_WIDTH}')
+    if H * H + W * W >= 1 << 30 or N > 65535 or N * H * W >= 1 << 31:
+        raise LednError(f'{who}: {N} x {H} x {W}: H^2 + W^2 must stay below 2^30, N at most 65535, N*H*W below 2^31')
+
+
+def edt_sq(mask):
+    """The exact squared Euclidean distance transform: mask uint8 (or bool) [N,H,W], non-zero = foreground -> int32
+    [N,H,W], for a foreground pixel the squared distance to the nearest background pixel of its image, 0 on background.
+    An image without a background pixel gets (y + 1)^2 + x^2 (what scipy returns for such a mask)."""
+    who = 'edt_sq'
+    lib = _lib.get_lib()
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.uint8, torch.bool) or mask.dim() != 3 or mask.numel() == 0:
+        raise LednError(f'{who}: a non-empty uint8 or bool mask [N,H,W] required')
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    N, H, W = (int(v) for v in mask.shape)
+    _edt_shape(who, N, H, W)
+    out = torch.empty((N, H, W), dtype=torch.int32, device=mask.device)
+    _check(lib, mask, out)
+    timing = _ops._TIMING is not None and (f'{who} {N}x{H}x{W}', 13 * mask.numel(), 8 * mask.numel(), 'hd_row_kernel')
+    _run(lib, 'ledn_edt_sq', mask, _p(mask), N, H, W, _p(out), work=timing)
+    return out
+
+
+def _hausdorff_args(who, logits, target):
+    lib, N, shape, P = _seg_loss_args(who, logits, target, False, 'mean')
+    H, W, Cc = int(target.shape[1]), int(target.shape[2]), int(logits.shape[-1])
+    if Cc > HAUSDORFF_MAX_CLASSES:
+        raise LednError(f'{who}: {Cc} classes; the Hausdorff kernels take at most {HAUSDORFF_MAX_CLASSES}')
+    _edt_shape(who, N, H, W)
+    return lib, (N, H, W, Cc), P
+
+
+def hausdorff_loss_fwd(logits, target, loss_weight=1.0, ignore_index=255, acc_ignore_index=255):
+    """HuasdorffDisstanceLoss: logits [N,H,W,C] f32, target [N,H,W] int64 -> (out[4] = loss, acc, the divisor C*N*H*W,
+    #pixels of the accuracy ; work, which holds D = d_seg^2 + d_gt^2 for the backward).  ignore_index: the label that
+    counts as background with target 0 in the loss; acc_ignore_index: the label left out of the accuracy."""
+    who = 'hausdorff_loss'
+    lib, shape, P = _hausdorff_args(who, logits, target)
+    nbytes = lib.cdll.ledn_hausdorff_work_bytes(*shape)
+    if nbytes <= 0:
+        raise LednError(f'{who}: shape outside the kernels\' limits')
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=logits.device)
+    out = torch.empty(4, dtype=torch.float32, device=logits.device)
+    _check(lib, logits, target, work, out)
+    Cc = shape[3]
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{Cc}', 2 * _nb(logits, target) + 44 * P, 12 * P * Cc, 'hd_row_kernel')
+    _run(lib, 'ledn_hausdorff_loss_fwd', logits, _p(logits), _p(target), *shape, int(ignore_index), int(acc_ignore_index),
+         float(loss_weight), _p(work), _p(out), work=timing)
+    return out, work
+
+
+def hausdorff_loss_bwd(logits, target, work, out, dloss):
+    """-> dlogits (one streaming kernel: the softmax again, D and the scale out of the forward's work buffer)"""
+    who = 'hausdorff_loss_bwd'
+    lib, shape, P = _hausdorff_args(who, logits, target)
+    if (not torch.is_tensor(work) or work.dtype != torch.float32 or work.dim() != 1
+            or work.numel() * 4 < lib.cdll.ledn_hausdorff_work_bytes(*shape)):
+        raise LednError(f'{who}: work is not the forward\'s (too small for {shape[0]} x {shape[1]} x {shape[2]} pixels)')
+    dl = torch.empty_like(logits)
+    dloss = dloss.reshape(1).to(torch.float32).contiguous()
+    _check(lib, logits, target, work, out, dloss, dl)
+    Cc = shape[3]
+    timing = _ops._TIMING is not None and (f'{who} P{P} C{Cc}', _nb(logits, target, dl) + 4 * P, 16 * P * Cc, 'hd_bwd_kernel')
+    _run(lib, 'ledn_hausdorff_loss_bwd', logits, _p(logits), _p(target), *shape, _p(work), _p(dloss), _p(dl), work=timing)
+    return dl
+
+
 def mfaf_ctx_fwd(pooled, seqs, training, stats1=None, momentum=0.1, tails=None, sync=None, world=1):
     """The four pooled-context MLPs of Muti_AFF in one launch sequence (ledn_mfaf_ctx_fwd).
     pooled: 4 f32 [N,S,S,C] maps; seqs: 4 x (conv1, bn1, conv2) modules.  -> (z2 list [N,S,S,C] f32, saved dict)

@@ -1389,12 +1389,12 @@ class OhemUp2Fn(Function):
 class SegLossFn(Function):
     """CrossEntropyLoss / DiceLoss / FocalLoss / TverskyLoss through csrc/seg_loss.hip: on NHWC logits (up = False) or
     on resize(src -> label size) with the exact 2x resize folded into the kernels (up = True).  LovaszLoss through
-    csrc/lovasz.hip, on NHWC logits only.  -> (loss, out[4])"""
+    csrc/lovasz.hip and HuasdorffDisstanceLoss through csrc/hausdorff.hip, on NHWC logits only.  -> (loss, out[4])"""
 
     @staticmethod
     def forward(ctx, x, target, family, up, fwd_kw, bwd_kw):
-        if up and family == 'lovasz':
-            raise ValueError('LovaszLoss has no resize-folded form: it runs on the full-resolution logits')
+        if up and family in UNFOLDED_FAMILIES:
+            raise ValueError(f'the {family} loss has no resize-folded form: it runs on the full-resolution logits')
         fwd = getattr(T, f'{family}_loss_up_fwd' if up else f'{family}_loss_fwd')
         out, work = fwd(x, target, **fwd_kw)
         ctx.save_for_backward(x, target, work, out)
@@ -1411,6 +1411,16 @@ class SegLossFn(Function):
         family, up, bwd_kw = ctx.cfg
         bwd = getattr(T, f'{family}_loss_up_bwd' if up else f'{family}_loss_bwd')
         return bwd(x, target, work, out, dloss, **bwd_kw), None, None, None, None, None
+
+
+UNFOLDED_FAMILIES = ('lovasz', 'hausdorff')      # kernels without a resize-folded (`up`) form
+
+
+def runs_unfolded(crit):
+    """a loss whose kernels need the full-resolution logits (a ranking of all pixels, a distance transform): its entry
+    of loss_decode leaves the resize fold"""
+    from .losses import HuasdorffDisstanceLoss, LovaszLoss
+    return isinstance(crit, (LovaszLoss, HuasdorffDisstanceLoss))
 
 
 def seg_loss_apply(crit, x, target, up, ignore_index):
@@ -1448,16 +1458,16 @@ def led_head_loss_by_feat(h, seg_logits, batch_data_samples):
     c0, c1 = h.loss_decode[0], h.loss_decode[1]
     H, W = hw
     fold = bool(FUSE_LOSS_RESIZE and H % 2 == 0 and W % 2 == 0 and xc.shape[-1] == 2)
-    from .losses import LovaszLoss, OhemCrossEntropy
+    from .losses import OhemCrossEntropy
     if not (isinstance(c0, OhemCrossEntropy) and isinstance(c1, OhemCrossEntropy)):
-        # a CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss or LovaszLoss somewhere: each entry runs on its own
-        # (csrc/seg_loss.hip for the first four, csrc/lovasz.hip, the single-loss OHEM kernels for an OhemCrossEntropy
-        # next to one of them)
+        # a CrossEntropyLoss, DiceLoss, FocalLoss, TverskyLoss, LovaszLoss or HuasdorffDisstanceLoss somewhere: each
+        # entry runs on its own (csrc/seg_loss.hip for the first four, csrc/lovasz.hip, csrc/hausdorff.hip, the
+        # single-loss OHEM kernels for an OhemCrossEntropy next to one of them)
         losses, outs = [], []
         for crit, logit in ((c0, xc), (c1, xs)):
-            # a LovaszLoss ranks the full-resolution logits (its kernels have no resize-folded form): that entry alone
-            # leaves the fold, the other one keeps it
-            up = fold and not isinstance(crit, LovaszLoss)
+            # a LovaszLoss ranks the full-resolution logits, a HuasdorffDisstanceLoss transforms their argmax mask (no
+            # resize-folded form of either): that entry alone leaves the fold, the other one keeps it
+            up = fold and not runs_unfolded(crit)
             x = fuse_loss_half(logit, h1, h2, hw) if up else fuse_loss(logit, h1, h2, hw)
             if isinstance(crit, OhemCrossEntropy):
                 l, out = (OhemUpFn if up else OhemFn).apply(x, y, crit.thresh, crit.min_kept, crit.loss_weight,
