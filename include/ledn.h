@@ -443,7 +443,12 @@ int ledn_window_attn(const void* qkv, const float* biasT, void* out, int N, int 
 /* The relative-position bias operand of ledn_window_attn from the module's parameters
  * (UNetFormer_GETB.py:181-187): biasT[h][j][i] = table[index[i*T + j]][h]; table [R = (2ws-1)^2][heads] f32,
  * index [T*T] int64 (the module's registered buffer), T = ws*ws.  _bwd: dtable[r][h] += sum of dbiasT over the
- * token pairs that index row r (gather form, deterministic).  Replaces the host-side index / index_put chain. */
+ * token pairs that index row r (gather form, deterministic).  Replaces the host-side index / index_put chain.
+ * R <= 1024.  Index entries outside [0, R) read as 0 and receive no gradient.
+ * In deterministic mode (LEDN_OPT_DETERMINISTIC) _bwd sums in 64-bit fixed point (scale 2^40, resolution 9e-13):
+ * each finite dbiasT value is clamped into +-8e6 before the conversion, so a larger magnitude saturates there
+ * (the sum of a row wraps beyond +-8.3e6).  A NaN or Inf in dbiasT makes exactly the dtable entries it maps to
+ * non-finite (+Inf and -Inf on one entry: NaN), in both modes; every other entry is unaffected. */
 int ledn_relpos_bias(const float* table, const long long* index, float* biasT, int R, int heads, int T, void* stream);
 int ledn_relpos_bias_bwd(const float* dbiasT, const long long* index, float* dtable, int R, int heads, int T,
                          void* stream);

@@ -312,21 +312,39 @@ __global__ void __launch_bounds__(256) relpos_bias_bwd_kernel(const float* dbias
         // deterministic mode: the same scatter, accumulated as 64-bit FIXED-POINT integers (scale 2^40: resolution 9e-13,
         // range +-8e6) -- integer addition is associative, so the order in which the LDS atomics arrive does not matter.
         // (The first deterministic form, one thread per table row scanning the whole index map, took 414 us per launch.)
+        // A finite value outside +-8e6 is clamped into that range (include/ledn.h).  A NaN or Inf has no fixed-point form:
+        // it is kept out of the integer sum and recorded per table row instead (integer max: order-free like the sum), so
+        // that exactly the entries it maps to come out non-finite, as in the default mode.
         __shared__ unsigned long long s_q[RMAX];
-        for (int i = threadIdx.x; i < R; i += 256) s_q[i] = 0ull;
+        __shared__ unsigned s_hi[RMAX], s_lo[RMAX];      // s_hi: 1 = +Inf seen, 2 = NaN seen; s_lo: 1 = -Inf seen
+        for (int i = threadIdx.x; i < R; i += 256) {
+            s_q[i] = 0ull;
+            s_hi[i] = 0u;
+            s_lo[i] = 0u;
+        }
         __syncthreads();
         for (int e = threadIdx.x; e < T * T; e += 256) {
             const int i = e / T, j = e % T;
             const long long r = index[e];
             if (r >= 0 && r < R) {
                 const float v = dbias[((long)h * T + j) * T + i];
-                const long long q = (long long)llrintf(fminf(fmaxf(v, -8.0e6f), 8.0e6f) * 1099511627776.f);
-                atomicAdd(&s_q[r], (unsigned long long)q);
+                if (v != v) atomicMax(&s_hi[r], 2u);
+                else if (v == __builtin_huge_valf()) atomicMax(&s_hi[r], 1u);
+                else if (v == -__builtin_huge_valf()) atomicMax(&s_lo[r], 1u);
+                else {
+                    const long long q = (long long)llrintf(fminf(fmaxf(v, -8.0e6f), 8.0e6f) * 1099511627776.f);
+                    atomicAdd(&s_q[r], (unsigned long long)q);
+                }
             }
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < R; i += 256)
-            dtable[(long)i * heads + h] += (float)((double)(long long)s_q[i] * (1.0 / 1099511627776.0));
+        for (int i = threadIdx.x; i < R; i += 256) {
+            float t = (float)((double)(long long)s_q[i] * (1.0 / 1099511627776.0));
+            if (s_hi[i] == 1u) t += __builtin_huge_valf();
+            if (s_lo[i] == 1u) t -= __builtin_huge_valf();       // +Inf and -Inf on one row: NaN, as a float sum gives
+            if (s_hi[i] == 2u) t = __builtin_nanf("");
+            dtable[(long)i * heads + h] += t;
+        }
         return;
     }
     for (int i = threadIdx.x; i < R; i += 256) s_t[i] = 0.f;

@@ -296,6 +296,14 @@ __device__ __forceinline__ Lerp lerp_coord(int dst, int in, int out) {
     l.w0 = 1.f - l.w1;
     return l;
 }
+// The blend of one channel of the planar-logit kernels (bilinear_nchw_kernel, tta_merge_kernel), whose outputs feed an
+// argmax.  Explicit fmaf: which product of a*b + c*d gets fused is otherwise the compiler's choice PER USE, and the
+// packed-math code of the two-class kernel chose differently for channel 0 and channel 1 -- classes with equal inputs
+// came out one ulp apart and the argmax of a tie was not the first class (tests/test_gather_ops.py).
+__device__ __forceinline__ float lerp_blend(const Lerp& ly, const Lerp& lx, float v00, float v01, float v10, float v11) {
+    const float t0 = fmaf(lx.w1, v01, lx.w0 * v00), t1 = fmaf(lx.w1, v11, lx.w0 * v10);
+    return fmaf(ly.w1, t1, ly.w0 * t0);
+}
 
 // ---- flat index -> (channel vector, x, y, image) --------------------------------------------------------
 // 32-bit divisions whenever the index fits (every tensor of this network: < 2^31 vectors); a 64-bit integer division is

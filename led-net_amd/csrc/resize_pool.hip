@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(256) bilinear_nchw_kernel(ledn_resize_desc d) 
     float bv = 0.f;
 #pragma unroll
     for (int i = 0; i < C; ++i) {
-        o[i] = ly.w0 * (lx.w0 * v00[i] + lx.w1 * v01[i]) + ly.w1 * (lx.w0 * v10[i] + lx.w1 * v11[i]);
+        o[i] = lerp_blend(ly, lx, v00[i], v01[i], v10[i], v11[i]);   // the same rounding sequence for every class
         if (d.add) o[i] += reinterpret_cast<const float*>(d.add)[pix * C + i];
         y[((long)n * C + i) * plane + (long)ho * d.Wo + wo] = o[i];
         if (i == 0 || o[i] > bv) {

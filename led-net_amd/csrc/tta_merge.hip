@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(256) tta_accumulate_kernel(ledn_tta_desc d) {
         float m = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {      // the arithmetic of bilinear_nchw_kernel
-            v[j][c] = ly.w0 * (lx.w0 * v00[c] + lx.w1 * v01[c]) + ly.w1 * (lx.w0 * v10[c] + lx.w1 * v11[c]);
+            v[j][c] = lerp_blend(ly, lx, v00[c], v01[c], v10[c], v11[c]);
             m = (c == 0 || v[j][c] > m) ? v[j][c] : m;
         }
         if (d.mode == LEDN_TTA_SOFTMAX) {
