@@ -28,6 +28,9 @@ extern "C" {
 #define LEDN_ABI_VERSION 5
 
 enum { LEDN_OK = 0, LEDN_EINVAL = 1, LEDN_ELAUNCH = 2, LEDN_ESKIP = 3 /* optional fast path not applicable: use the general entry */ };
+/* dtype codes.  Every entry returns LEDN_EINVAL for a code, or a combination of codes, that it has no kernel for; it
+ * never runs a kernel of another type in its place (LEDN_U8 is read only by the stem / input entries: ledn_stem_conv*,
+ * ledn_im2col_stem_planar, ledn_nchw_to_nhwc). */
 enum { LEDN_F32 = 0, LEDN_BF16 = 1, LEDN_U8 = 2 };
 enum { LEDN_ACT_NONE = 0, LEDN_ACT_RELU = 1, LEDN_ACT_RELU6 = 2, LEDN_ACT_PRELU = 3, LEDN_ACT_SIGMOID = 4 };
 enum { LEDN_RES_NONE = 0, LEDN_RES_ADD = 1, LEDN_RES_GATE = 2 }; /* v+res | v*res+res */

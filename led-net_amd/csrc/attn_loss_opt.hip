@@ -415,26 +415,24 @@ int window_attn_bwd_impl(const void* qkv, const float* biasT, const void* dout, 
         if (part) return finish_partials(part, (int)nb, heads * 64 * 64, 1, dbiasT, nullptr, nullptr, s);
         return check_launch();
     }
-#define LEDN_WB(T, DD)                                                                                  \
-    do {                                                                                                \
-        if (padded)                                                                                     \
-            LEDN_LAUNCH((window_attn_bwd_kernel<T, DD, true>), grid, dim3(64), 0, s, (const T*)qkv, biasT, \
-                        (const T*)dout, dqkv, dbiasT, N, H, W, C, heads, hh, ww, part, pad_out);        \
-        else                                                                                            \
-            LEDN_LAUNCH((window_attn_bwd_kernel<T, DD, false>), grid, dim3(64), 0, s, (const T*)qkv, biasT, \
-                        (const T*)dout, dqkv, dbiasT, N, H, W, C, heads, hh, ww, part, (float*)nullptr); \
+    const int rc = with_dtype(dtype, [&](auto t) -> int {
+        using T = tag_t<decltype(t)>;
+#define LEDN_WB(DD)                                                                                                 \
+    do {                                                                                                            \
+        if (padded)                                                                                                 \
+            LEDN_LAUNCH((window_attn_bwd_kernel<T, DD, true>), grid, dim3(64), 0, s, (const T*)qkv, biasT,          \
+                        (const T*)dout, dqkv, dbiasT, N, H, W, C, heads, hh, ww, part, pad_out);                    \
+        else                                                                                                        \
+            LEDN_LAUNCH((window_attn_bwd_kernel<T, DD, false>), grid, dim3(64), 0, s, (const T*)qkv, biasT,         \
+                        (const T*)dout, dqkv, dbiasT, N, H, W, C, heads, hh, ww, part, (float*)nullptr);            \
     } while (0)
-#define LEDN_WBD(T)                        \
-    do {                                   \
-        if (D == 16) LEDN_WB(T, 16);       \
-        else if (D == 32) LEDN_WB(T, 32);  \
-        else return LEDN_EINVAL;           \
-    } while (0)
-    if (dtype == LEDN_F32) LEDN_WBD(float);
-    else if (dtype == LEDN_BF16) LEDN_WBD(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_WBD
+        if (D == 16) LEDN_WB(16);
+        else if (D == 32) LEDN_WB(32);
+        else return LEDN_EINVAL;
 #undef LEDN_WB
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     if (pad_out) {
         const long total = (long)N * H * W * 3 * C;
         LEDN_LAUNCH(window_attn_fold_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, pad_out, dqkv, N, H, W,

@@ -192,26 +192,6 @@ static int bnbwd_validate(const ledn_bnbwd_desc& d, bool apply) {
     return LEDN_OK;
 }
 
-#define LEDN_BNB_DISPATCH(KERNEL, ...)                                                                   \
-    do {                                                                                                 \
-        const bool v4 = d.C % 4 == 0;                                                                    \
-        if (false && d.dtype_z == LEDN_BF16 && d.dtype_y == LEDN_BF16 && d.C % 8 == 0) { /* 16 B/lane: slower */ \
-            LEDN_LAUNCH((KERNEL<bf16_t, bf16_t, 8>), grid, dim3(256), 0, s, __VA_ARGS__);                \
-        } else if (d.dtype_z == LEDN_F32 && d.dtype_y == LEDN_F32) {                                     \
-            if (v4) LEDN_LAUNCH((KERNEL<float, float, 4>), grid, dim3(256), 0, s, __VA_ARGS__);          \
-            else LEDN_LAUNCH((KERNEL<float, float, 1>), grid, dim3(256), 0, s, __VA_ARGS__);             \
-        } else if (d.dtype_z == LEDN_BF16 && d.dtype_y == LEDN_BF16) {                                   \
-            if (v4) LEDN_LAUNCH((KERNEL<bf16_t, bf16_t, 4>), grid, dim3(256), 0, s, __VA_ARGS__);        \
-            else LEDN_LAUNCH((KERNEL<bf16_t, bf16_t, 1>), grid, dim3(256), 0, s, __VA_ARGS__);           \
-        } else if (d.dtype_z == LEDN_BF16 && d.dtype_y == LEDN_F32) {                                    \
-            if (v4) LEDN_LAUNCH((KERNEL<bf16_t, float, 4>), grid, dim3(256), 0, s, __VA_ARGS__);         \
-            else LEDN_LAUNCH((KERNEL<bf16_t, float, 1>), grid, dim3(256), 0, s, __VA_ARGS__);            \
-        } else if (d.dtype_z == LEDN_F32 && d.dtype_y == LEDN_BF16) {                                    \
-            if (v4) LEDN_LAUNCH((KERNEL<float, bf16_t, 4>), grid, dim3(256), 0, s, __VA_ARGS__);         \
-            else LEDN_LAUNCH((KERNEL<float, bf16_t, 1>), grid, dim3(256), 0, s, __VA_ARGS__);            \
-        } else return LEDN_EINVAL;                                                                       \
-    } while (0)
-
 static long bn_rows(const ledn_bnbwd_desc& d) {
     const int V = d.C % 4 == 0 ? 4 : 1;
     return 256 / (d.C / V);
@@ -243,7 +223,15 @@ int bn_act_bwd_reduce_impl(const ledn_bnbwd_desc& d0, hipStream_t s) {
     if (nb > 64 || det()) part = ws_take(nb * 3 * d.C);
     if (!part && nb > 256) nb = 256;     // atomics fallback: keep the grid bounded
     const dim3 grid((unsigned)nb);
-    LEDN_BNB_DISPATCH(bn_bwd_reduce_kernel, d, part);
+    const bool v4 = d.C % 4 == 0;   // 16 B per lane (V = 8, bf16) measured slower
+    const int rl = with_dtypes(d.dtype_z, d.dtype_y, [&](auto tz, auto ty) {
+        using TZ = tag_t<decltype(tz)>;
+        using TY = tag_t<decltype(ty)>;
+        if (v4) LEDN_LAUNCH((bn_bwd_reduce_kernel<TZ, TY, 4>), grid, dim3(256), 0, s, d, part);
+        else LEDN_LAUNCH((bn_bwd_reduce_kernel<TZ, TY, 1>), grid, dim3(256), 0, s, d, part);
+        return LEDN_OK;
+    });
+    if (rl != LEDN_OK) return rl;
     if (part) return finish_partials(part, (int)nb, d.C, 3, d.sum_g, d.sum_gx, d.dslope, s);
     return check_launch();
 }
@@ -260,8 +248,14 @@ int bn_act_bwd_apply_impl(const ledn_bnbwd_desc& d0, hipStream_t s) {
     long nb = cdiv(d.P, bn_rows(d) * 4);
     if (nb > 4096) nb = 4096;
     const dim3 grid((unsigned)nb);
-    LEDN_BNB_DISPATCH(bn_bwd_apply_kernel, d);
-    return check_launch();
+    const bool v4 = d.C % 4 == 0;   // 16 B per lane (V = 8, bf16) measured slower
+    return with_dtypes(d.dtype_z, d.dtype_y, [&](auto tz, auto ty) {
+        using TZ = tag_t<decltype(tz)>;
+        using TY = tag_t<decltype(ty)>;
+        if (v4) LEDN_LAUNCH((bn_bwd_apply_kernel<TZ, TY, 4>), grid, dim3(256), 0, s, d);
+        else LEDN_LAUNCH((bn_bwd_apply_kernel<TZ, TY, 1>), grid, dim3(256), 0, s, d);
+        return check_launch();
+    });
 }
 
 // ===========================================================================
@@ -567,16 +561,12 @@ int dw_bwd_data_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
     const bool v4 = d.C % 4 == 0 && d.group_size % 4 == 0;
     const long total = (long)d.N * d.H * d.W * (v4 ? d.C / 4 : d.C);
     const dim3 grid((unsigned)cdiv(total, 256));
-#define LEDN_K(T)                                                                     \
-    do {                                                                              \
-        if (v4) LEDN_LAUNCH((dw_bwd_data_kernel<T, 4>), grid, dim3(256), 0, s, d);    \
-        else LEDN_LAUNCH((dw_bwd_data_kernel<T, 1>), grid, dim3(256), 0, s, d);       \
-    } while (0)
-    if (d.dtype == LEDN_F32) LEDN_K(float);
-    else if (d.dtype == LEDN_BF16) LEDN_K(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_K
-    return check_launch();
+    return with_dtype(d.dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4) LEDN_LAUNCH((dw_bwd_data_kernel<T, 4>), grid, dim3(256), 0, s, d);
+        else LEDN_LAUNCH((dw_bwd_data_kernel<T, 1>), grid, dim3(256), 0, s, d);
+        return check_launch();
+    });
 }
 
 int dw3x3_bwd_weight_bf16(const ledn_dwbwd_desc& d, hipStream_t s);   // stencil_bf16.hip; -1 = shape not covered
@@ -605,9 +595,11 @@ int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
         float* part = (nb > 32 || det()) ? ws_take(nb * 9 * d.C) : nullptr;
         if (!part && nb > 128) nb = 128;
         const dim3 g3((unsigned)nb);
-        if (d.dtype == LEDN_F32) LEDN_LAUNCH((dw_bwd_weight3x3_kernel<float, 4>), g3, dim3(256), 0, s, d, part);
-        else if (d.dtype == LEDN_BF16) LEDN_LAUNCH((dw_bwd_weight3x3_kernel<bf16_t, 4>), g3, dim3(256), 0, s, d, part);
-        else return LEDN_EINVAL;
+        rc = with_dtype(d.dtype, [&](auto t) {
+            LEDN_LAUNCH((dw_bwd_weight3x3_kernel<tag_t<decltype(t)>, 4>), g3, dim3(256), 0, s, d, part);
+            return LEDN_OK;
+        });
+        if (rc != LEDN_OK) return rc;
         if (part) return finish_partials(part, (int)nb, 9 * d.C, 1, d.dw, nullptr, nullptr, s);
         return check_launch();
     }
@@ -622,9 +614,11 @@ int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
             nbx = cdiv(npix, ppb);
         }
         const dim3 g8((unsigned)nbx, (unsigned)d.KH);
-        if (d.dtype == LEDN_F32) LEDN_LAUNCH((dw_bwd_weight_row_kernel<float, 4, 8>), g8, dim3(256), 0, s, d, (int)ppb, part);
-        else if (d.dtype == LEDN_BF16) LEDN_LAUNCH((dw_bwd_weight_row_kernel<bf16_t, 4, 8>), g8, dim3(256), 0, s, d, (int)ppb, part);
-        else return LEDN_EINVAL;
+        rc = with_dtype(d.dtype, [&](auto t) {
+            LEDN_LAUNCH((dw_bwd_weight_row_kernel<tag_t<decltype(t)>, 4, 8>), g8, dim3(256), 0, s, d, (int)ppb, part);
+            return LEDN_OK;
+        });
+        if (rc != LEDN_OK) return rc;
         if (part) return finish_partials(part, (int)nbx, d.KH * 8 * d.C, 1, d.dw, nullptr, nullptr, s);
         return check_launch();
     }
@@ -641,15 +635,13 @@ int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
         nbx = cdiv(npix, ppb);
     }
     const dim3 grid((unsigned)nbx, (unsigned)taps);
-#define LEDN_K(T)                                                                                       \
-    do {                                                                                                \
-        if (v4) LEDN_LAUNCH((dw_bwd_weight_kernel<T, 4>), grid, dim3(256), 0, s, d, (int)ppb, part);    \
-        else LEDN_LAUNCH((dw_bwd_weight_kernel<T, 1>), grid, dim3(256), 0, s, d, (int)ppb, part);       \
-    } while (0)
-    if (d.dtype == LEDN_F32) LEDN_K(float);
-    else if (d.dtype == LEDN_BF16) LEDN_K(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_K
+    rc = with_dtype(d.dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4) LEDN_LAUNCH((dw_bwd_weight_kernel<T, 4>), grid, dim3(256), 0, s, d, (int)ppb, part);
+        else LEDN_LAUNCH((dw_bwd_weight_kernel<T, 1>), grid, dim3(256), 0, s, d, (int)ppb, part);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     if (part) return finish_partials(part, (int)nbx, taps * d.C, 1, d.dw, nullptr, nullptr, s);
     return check_launch();
 }
@@ -801,20 +793,17 @@ int pyr_bwd_data_impl(const ledn_pyrbwd_desc& d, hipStream_t s) {
         if (rc >= 0) return rc;
     }
     const dim3 g1((unsigned)cdiv(npo * cvn, 256)), g2((unsigned)cdiv((long)d.N * d.H * d.W * cvn, 256));
-#define LEDN_K(T)                                                                                          \
-    do {                                                                                                   \
-        if (v4) {                                                                                          \
-            LEDN_LAUNCH((pyr_suffix_kernel<T, 4>), g1, dim3(256), 0, s, (const T*)d.dy, (T*)d.gsum, npo, d.n); \
-            LEDN_LAUNCH((pyr_bwd_data_kernel<T, 4>), g2, dim3(256), 0, s, d);                              \
-        } else {                                                                                           \
-            LEDN_LAUNCH((pyr_suffix_kernel<T, 1>), g1, dim3(256), 0, s, (const T*)d.dy, (T*)d.gsum, npo, d.n); \
-            LEDN_LAUNCH((pyr_bwd_data_kernel<T, 1>), g2, dim3(256), 0, s, d);                              \
-        }                                                                                                  \
-    } while (0)
-    if (d.dtype == LEDN_F32) LEDN_K(float);
-    else LEDN_K(bf16_t);
-#undef LEDN_K
-    return check_launch();
+    return with_dtype(d.dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4) {
+            LEDN_LAUNCH((pyr_suffix_kernel<T, 4>), g1, dim3(256), 0, s, (const T*)d.dy, (T*)d.gsum, npo, d.n);
+            LEDN_LAUNCH((pyr_bwd_data_kernel<T, 4>), g2, dim3(256), 0, s, d);
+        } else {
+            LEDN_LAUNCH((pyr_suffix_kernel<T, 1>), g1, dim3(256), 0, s, (const T*)d.dy, (T*)d.gsum, npo, d.n);
+            LEDN_LAUNCH((pyr_bwd_data_kernel<T, 1>), g2, dim3(256), 0, s, d);
+        }
+        return check_launch();
+    });
 }
 
 // which kernel pyr_bwd_data_impl launches for d: 0 pyr_bwd_data_kernel, 1 pyr_bwd_data_bf16_kernel (both after
@@ -846,14 +835,13 @@ int pyr_bwd_weight_impl(const ledn_pyrbwd_desc& d, hipStream_t s) {
     float* part = (nb > 32 || det()) ? ws_take(nb * 36 * d.n) : nullptr;
     if (!part && nb > 128) nb = 128;
     const dim3 grid((unsigned)nb, 4u);
-#define LEDN_K(T)                                                                              \
-    do {                                                                                       \
-        if (v4) LEDN_LAUNCH((pyr_bwd_weight_kernel<T, 4>), grid, dim3(256), 0, s, d, part);    \
-        else LEDN_LAUNCH((pyr_bwd_weight_kernel<T, 1>), grid, dim3(256), 0, s, d, part);       \
-    } while (0)
-    if (d.dtype == LEDN_F32) LEDN_K(float);
-    else LEDN_K(bf16_t);
-#undef LEDN_K
+    rc = with_dtype(d.dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4) LEDN_LAUNCH((pyr_bwd_weight_kernel<T, 4>), grid, dim3(256), 0, s, d, part);
+        else LEDN_LAUNCH((pyr_bwd_weight_kernel<T, 1>), grid, dim3(256), 0, s, d, part);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     if (part) return finish_partials(part, (int)nb, 36 * d.n, 1, d.dw, nullptr, nullptr, s);
     return check_launch();
 }
@@ -1032,22 +1020,21 @@ int bilinear_bwd_impl(const void* dy, void* dx, int N, int H, int W, int C, int 
     // >= 4x and few source pixels: one workgroup per source pixel (see bilinear_bwd_wide_kernel)
     const bool wide = v4 && !x2 && Ho >= 4 * H && Wo >= 4 * W && C / 4 <= 256 && (long)N * H * W <= (1L << 20) &&
                       (options().stream_fast & 2);
-#define LEDN_K(TY, TX)                                                                                          \
-    do {                                                                                                        \
-        if (wide) LEDN_LAUNCH((bilinear_bwd_wide_kernel<TY, TX>), dim3((unsigned)((long)N * H * W)), dim3(256), 0, s, (const TY*)dy, (TX*)dx, N, H, W, C, Ho, Wo); \
-        else if (x2 && v4) LEDN_LAUNCH((bilinear_bwd2x_kernel<TY, TX, 4>), grid, dim3(256), 0, s, (const TY*)dy, (TX*)dx, N, H, W, C); \
-        else if (x2 && v2) LEDN_LAUNCH((bilinear_bwd2x_kernel<TY, TX, 2>), grid, dim3(256), 0, s, (const TY*)dy, (TX*)dx, N, H, W, C); \
-        else if (v4) LEDN_LAUNCH((bilinear_bwd_kernel<TY, TX, 4>), grid, dim3(256), 0, s, (const TY*)dy, (TX*)dx, N, H, W, C, Ho, Wo); \
-        else if (v2) LEDN_LAUNCH((bilinear_bwd_kernel<TY, TX, 2>), grid, dim3(256), 0, s, (const TY*)dy, (TX*)dx, N, H, W, C, Ho, Wo); \
-        else LEDN_LAUNCH((bilinear_bwd_kernel<TY, TX, 1>), grid, dim3(256), 0, s, (const TY*)dy, (TX*)dx, N, H, W, C, Ho, Wo); \
-    } while (0)
-    if (dtype_dy == LEDN_F32 && dtype_dx == LEDN_F32) LEDN_K(float, float);
-    else if (dtype_dy == LEDN_BF16 && dtype_dx == LEDN_BF16) LEDN_K(bf16_t, bf16_t);
-    else if (dtype_dy == LEDN_F32 && dtype_dx == LEDN_BF16) LEDN_K(float, bf16_t);
-    else if (dtype_dy == LEDN_BF16 && dtype_dx == LEDN_F32) LEDN_K(bf16_t, float);
-    else return LEDN_EINVAL;
-#undef LEDN_K
-    return check_launch();
+    return with_dtypes(dtype_dy, dtype_dx, [&](auto ty, auto tx) {
+        using TY = tag_t<decltype(ty)>;
+        using TX = tag_t<decltype(tx)>;
+        const TY* g = (const TY*)dy;
+        TX* o = (TX*)dx;
+        if (wide)
+            LEDN_LAUNCH((bilinear_bwd_wide_kernel<TY, TX>), dim3((unsigned)((long)N * H * W)), dim3(256), 0, s, g, o, N, H, W, C,
+                        Ho, Wo);
+        else if (x2 && v4) LEDN_LAUNCH((bilinear_bwd2x_kernel<TY, TX, 4>), grid, dim3(256), 0, s, g, o, N, H, W, C);
+        else if (x2 && v2) LEDN_LAUNCH((bilinear_bwd2x_kernel<TY, TX, 2>), grid, dim3(256), 0, s, g, o, N, H, W, C);
+        else if (v4) LEDN_LAUNCH((bilinear_bwd_kernel<TY, TX, 4>), grid, dim3(256), 0, s, g, o, N, H, W, C, Ho, Wo);
+        else if (v2) LEDN_LAUNCH((bilinear_bwd_kernel<TY, TX, 2>), grid, dim3(256), 0, s, g, o, N, H, W, C, Ho, Wo);
+        else LEDN_LAUNCH((bilinear_bwd_kernel<TY, TX, 1>), grid, dim3(256), 0, s, g, o, N, H, W, C, Ho, Wo);
+        return check_launch();
+    });
 }
 
 // ===========================================================================
@@ -1169,16 +1156,16 @@ int avgpool3x3s2_bwd_impl(const void* dy, const void* add, void* dx, int N, int 
     const bool v4 = C % 4 == 0;
     const long total = (long)N * H * W * (v4 ? C / 4 : C);
     const dim3 grid((unsigned)cdiv(total, 256));
-#define LEDN_K(T)                                                                                            \
-    do {                                                                                                     \
-        if (v4) LEDN_LAUNCH((avgpool3x3s2_bwd_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)dy, (const T*)add, (T*)dx, N, H, W, C, Ho, Wo); \
-        else LEDN_LAUNCH((avgpool3x3s2_bwd_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)dy, (const T*)add, (T*)dx, N, H, W, C, Ho, Wo);    \
-    } while (0)
-    if (dtype == LEDN_F32) LEDN_K(float);
-    else if (dtype == LEDN_BF16) LEDN_K(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_K
-    return check_launch();
+    return with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4)
+            LEDN_LAUNCH((avgpool3x3s2_bwd_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)dy, (const T*)add, (T*)dx, N, H, W, C,
+                        Ho, Wo);
+        else
+            LEDN_LAUNCH((avgpool3x3s2_bwd_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)dy, (const T*)add, (T*)dx, N, H, W, C,
+                        Ho, Wo);
+        return check_launch();
+    });
 }
 
 // ===========================================================================
@@ -1237,14 +1224,11 @@ int getb_pool_bwd_impl(const void* dout, void* da, int N, int H, int W, int C, i
     LEDN_REQUIRE(dout && da && N > 0 && H >= 2 && W >= 2 && C > 0 && ws >= 2 && C % 4 == 0);
     const long total = (long)N * H * W * (C / 4);
     const dim3 grid((unsigned)cdiv(total, 256));
-    if (dtype == LEDN_F32)
-        LEDN_LAUNCH((getb_pool_bwd_kernel<float, 4>), grid, dim3(256), 0, s, (const float*)dout, (float*)da, N,
-                    H, W, C, ws);
-    else if (dtype == LEDN_BF16)
-        LEDN_LAUNCH((getb_pool_bwd_kernel<bf16_t, 4>), grid, dim3(256), 0, s, (const bf16_t*)dout,
-                    (bf16_t*)da, N, H, W, C, ws);
-    else return LEDN_EINVAL;
-    return check_launch();
+    return with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        LEDN_LAUNCH((getb_pool_bwd_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)dout, (T*)da, N, H, W, C, ws);
+        return check_launch();
+    });
 }
 
 // ===========================================================================
@@ -1441,32 +1425,32 @@ int mfaf_gate_bwd_impl(const ledn_mfafbwd_desc& d, hipStream_t s) {
     for (int k = 0; k < 5; ++k) LEDN_REQUIRE(d.scale[k] && d.shift[k]);
     const dim3 grid((unsigned)(d.N * d.H), (unsigned)cdiv(d.W, MFAF_SEG));
     const int ctx_sums = det() ? 0 : 1;
-    if (d.dtype != LEDN_F32 && d.dtype != LEDN_BF16) return LEDN_EINVAL;
-    // (a 16-byte-lane form with each lane's <= 4 pixels requested up front -- the forward's mfaf_gate_fast_kernel shape --
-    //  measured 152 us against this kernel's 87 at 16 x 128 x 128 x 64: 198 registers, two workgroups per CU; not kept)
-    if (d.dtype == LEDN_F32) LEDN_LAUNCH((mfaf_gate_bwd_kernel<float, 4>), grid, dim3(256), 0, s, d, ctx_sums);
-    else LEDN_LAUNCH((mfaf_gate_bwd_kernel<bf16_t, 4>), grid, dim3(256), 0, s, d, ctx_sums);
-    if (!ctx_sums) {
-        for (int k = 0; k < 4; ++k) {
-            const int S = d.ctx_size[k];
-            // ~256 pixels per workgroup: row chunks per cell (a function of the shapes only: fixed summation order)
-            long nch = ((long)(d.H / S) * (d.W / S)) / 256;
-            if (nch < 1) nch = 1;
-            if (nch > 64) nch = 64;
-            if (nch > cdiv(d.H, S)) nch = cdiv(d.H, S);
-            const long cells = (long)d.N * S * S * d.C;
-            float* part = nch > 1 ? ws_take(nch * cells) : nullptr;
-            if (nch > 1 && !part) return LEDN_EINVAL;
-            const dim3 g2((unsigned)(d.N * S * S), (unsigned)nch);
-            if (d.dtype == LEDN_F32) LEDN_LAUNCH((mfaf_dctx_det_kernel<float>), g2, dim3(256), 0, s, d, k, part);
-            else LEDN_LAUNCH((mfaf_dctx_det_kernel<bf16_t>), g2, dim3(256), 0, s, d, k, part);
-            if (part) {
-                const int rc = finish_partials(part, (int)nch, (int)cells, 1, d.dctx[k], nullptr, nullptr, s);
-                if (rc != LEDN_OK) return rc;
+    return with_dtype(d.dtype, [&](auto t) -> int {
+        using T = tag_t<decltype(t)>;
+        // (a 16-byte-lane form with each lane's <= 4 pixels requested up front -- the forward's mfaf_gate_fast_kernel shape
+        //  -- measured 152 us against this kernel's 87 at 16 x 128 x 128 x 64: 198 registers, two workgroups per CU; not kept)
+        LEDN_LAUNCH((mfaf_gate_bwd_kernel<T, 4>), grid, dim3(256), 0, s, d, ctx_sums);
+        if (!ctx_sums) {
+            for (int k = 0; k < 4; ++k) {
+                const int S = d.ctx_size[k];
+                // ~256 pixels per workgroup: row chunks per cell (a function of the shapes only: fixed summation order)
+                long nch = ((long)(d.H / S) * (d.W / S)) / 256;
+                if (nch < 1) nch = 1;
+                if (nch > 64) nch = 64;
+                if (nch > cdiv(d.H, S)) nch = cdiv(d.H, S);
+                const long cells = (long)d.N * S * S * d.C;
+                float* part = nch > 1 ? ws_take(nch * cells) : nullptr;
+                if (nch > 1 && !part) return LEDN_EINVAL;
+                const dim3 g2((unsigned)(d.N * S * S), (unsigned)nch);
+                LEDN_LAUNCH((mfaf_dctx_det_kernel<T>), g2, dim3(256), 0, s, d, k, part);
+                if (part) {
+                    const int rc = finish_partials(part, (int)nch, (int)cells, 1, d.dctx[k], nullptr, nullptr, s);
+                    if (rc != LEDN_OK) return rc;
+                }
             }
         }
-    }
-    return check_launch();
+        return check_launch();
+    });
 }
 
 struct PoolSet {
@@ -1547,14 +1531,11 @@ int mfaf_bwd_combine_impl(void* dx, void* dr, const void* dxl, const float* cons
     }
     const long total = (long)N * H * W * (C / 4);
     const dim3 grid((unsigned)cdiv(total, 256));
-    if (dtype == LEDN_F32)
-        LEDN_LAUNCH((mfaf_combine_kernel<float, 4>), grid, dim3(256), 0, s, (float*)dx, (float*)dr,
-                    (const float*)dxl, ps, N, H, W, C);
-    else if (dtype == LEDN_BF16)
-        LEDN_LAUNCH((mfaf_combine_kernel<bf16_t, 4>), grid, dim3(256), 0, s, (bf16_t*)dx, (bf16_t*)dr,
-                    (const bf16_t*)dxl, ps, N, H, W, C);
-    else return LEDN_EINVAL;
-    return check_launch();
+    return with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        LEDN_LAUNCH((mfaf_combine_kernel<T, 4>), grid, dim3(256), 0, s, (T*)dx, (T*)dr, (const T*)dxl, ps, N, H, W, C);
+        return check_launch();
+    });
 }
 
 }  // namespace ledn

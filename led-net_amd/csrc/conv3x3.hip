@@ -1166,16 +1166,13 @@ int stem_conv_reg_impl(const void* x, int dtype_x, const void* wp, void* y, int 
     const long cap = (long)options().conv_workgroups * 4;
     if (nb > cap) nb = cap;
     a.part = (stat_sum && (nb > 16 || det())) ? ws_take(nb * 64) : nullptr;
-#define LEDN_STEMR(TX)                                                                                       \
-    do {                                                                                                     \
-        if (full) LEDN_LAUNCH((stem_conv_reg_kernel<TX, true>), dim3((unsigned)nb), dim3(256), 0, s, a);     \
-        else LEDN_LAUNCH((stem_conv_reg_kernel<TX, false>), dim3((unsigned)nb), dim3(256), 0, s, a);         \
-    } while (0)
-    if (dtype_x == LEDN_U8) LEDN_STEMR(unsigned char);
-    else if (dtype_x == LEDN_F32) LEDN_STEMR(float);
-    else if (dtype_x == LEDN_BF16) LEDN_STEMR(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_STEMR
+    const int rc = with_dtype_u8(dtype_x, [&](auto tx) {
+        using TX = tag_t<decltype(tx)>;
+        if (full) LEDN_LAUNCH((stem_conv_reg_kernel<TX, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+        else LEDN_LAUNCH((stem_conv_reg_kernel<TX, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     if (a.part) return finish_partials(a.part, (int)nb, 32, 2, stat_sum, stat_sqsum, nullptr, s);
     return check_launch();
 }
@@ -1416,16 +1413,14 @@ int stem_conv_wgrad_impl(const void* x, int dtype_x, const void* dz, float* dw, 
         a.b_sum_g = bn->sum_g; a.b_sum_gx = bn->sum_gx;
         a.b_inv_count = (float)(1.0 / bn->count);
         a.b_mode = bn->bn_mode; a.b_act = bn->act;
-        if (dtype_x == LEDN_U8) LEDN_LAUNCH((stem_wgrad_reg_kernel<unsigned char, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-        else if (dtype_x == LEDN_F32) LEDN_LAUNCH((stem_wgrad_reg_kernel<float, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-        else if (dtype_x == LEDN_BF16) LEDN_LAUNCH((stem_wgrad_reg_kernel<bf16_t, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-        else return LEDN_EINVAL;
-        return finish_partials(a.part, (int)nb, 864, 1, dw, nullptr, nullptr, s);
     }
-    if (dtype_x == LEDN_U8) LEDN_LAUNCH((stem_wgrad_reg_kernel<unsigned char, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
-    else if (dtype_x == LEDN_F32) LEDN_LAUNCH((stem_wgrad_reg_kernel<float, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
-    else if (dtype_x == LEDN_BF16) LEDN_LAUNCH((stem_wgrad_reg_kernel<bf16_t, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
-    else return LEDN_EINVAL;
+    const int rc = with_dtype_u8(dtype_x, [&](auto tx) {
+        using TX = tag_t<decltype(tx)>;
+        if (bn) LEDN_LAUNCH((stem_wgrad_reg_kernel<TX, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+        else LEDN_LAUNCH((stem_wgrad_reg_kernel<TX, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     return finish_partials(a.part, (int)nb, 864, 1, dw, nullptr, nullptr, s);
 }
 

@@ -376,22 +376,17 @@ int conv_direct(const ledn_conv_desc& d, hipStream_t s) {
         constexpr int UNR = 4;
         const int rows = 256 / (d.Cin >> 3);
         const dim3 grid((unsigned)cdiv((long)d.N * d.H * d.W, (long)rows * UNR));
-        if (d.dtype_y == LEDN_F32) LEDN_LAUNCH((conv1x1_narrow_kernel<float, UNR>), grid, dim3(256), 0, s, d);
-        else LEDN_LAUNCH((conv1x1_narrow_kernel<bf16_t, UNR>), grid, dim3(256), 0, s, d);
-        return check_launch();
+        return with_dtype(d.dtype_y, [&](auto ty) {
+            LEDN_LAUNCH((conv1x1_narrow_kernel<tag_t<decltype(ty)>, UNR>), grid, dim3(256), 0, s, d);
+            return check_launch();
+        });
     }
-    if (narrowin_ok(d)) {
-        if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_F32) return launch_narrowin<float, float>(d, s);
-        if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_BF16) return launch_narrowin<bf16_t, bf16_t>(d, s);
-        if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_F32) return launch_narrowin<bf16_t, float>(d, s);
-        if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_BF16) return launch_narrowin<float, bf16_t>(d, s);
-        return LEDN_EINVAL;
-    }
-    if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_F32) return launch_cot<float, float>(d, s);
-    if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_BF16) return launch_cot<bf16_t, bf16_t>(d, s);
-    if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_F32) return launch_cot<bf16_t, float>(d, s);
-    if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_BF16) return launch_cot<float, bf16_t>(d, s);
-    return LEDN_EINVAL;
+    const bool narrowin = narrowin_ok(d);
+    return with_dtypes(d.dtype_x, d.dtype_y, [&](auto tx, auto ty) {
+        using TX = tag_t<decltype(tx)>;
+        using TY = tag_t<decltype(ty)>;
+        return narrowin ? launch_narrowin<TX, TY>(d, s) : launch_cot<TX, TY>(d, s);
+    });
 }
 
 int conv_validate(const ledn_conv_desc& d) {
@@ -788,16 +783,14 @@ int conv_wgrad_cout2(const ledn_wgrad_desc& d, hipStream_t s) {
     float* part = (nb > 4 || det()) ? ws_take(nb * numel) : nullptr;
     if (!part && nb > 16) nb = 16;
     const dim3 grid((unsigned)nb);
-#define LEDN_C2(TZ)                                                                                   \
-    do {                                                                                              \
-        if (d.KH == 3) LEDN_LAUNCH((conv_wgrad_cout2_kernel<TZ, 3>), grid, dim3(256), 0, s, d, part); \
-        else LEDN_LAUNCH((conv_wgrad_cout2_kernel<TZ, 1>), grid, dim3(256), 0, s, d, part);           \
-    } while (0)
-    if (d.dtype_dz == LEDN_BF16) LEDN_C2(bf16_t);
-    else if (d.dtype_dz == LEDN_F32) LEDN_C2(float);
-    else return LEDN_EINVAL;
-#undef LEDN_C2
-    int rc = part ? finish_partials(part, (int)nb, (int)numel, 1, d.dw, nullptr, nullptr, s) : check_launch();
+    int rc = with_dtype(d.dtype_dz, [&](auto tz) {
+        using TZ = tag_t<decltype(tz)>;
+        if (d.KH == 3) LEDN_LAUNCH((conv_wgrad_cout2_kernel<TZ, 3>), grid, dim3(256), 0, s, d, part);
+        else LEDN_LAUNCH((conv_wgrad_cout2_kernel<TZ, 1>), grid, dim3(256), 0, s, d, part);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
+    rc = part ? finish_partials(part, (int)nb, (int)numel, 1, d.dw, nullptr, nullptr, s) : check_launch();
     if (rc != LEDN_OK || !d.db) return rc;
     return channel_stats_impl(d.dz, nullptr, npix, d.Cout, d.dtype_dz, d.db, nullptr, s);
 }
@@ -871,18 +864,15 @@ static int conv_wgrad_cin1(const ledn_wgrad_desc& d, hipStream_t s) {
     float* part = (nb > 4 || det()) ? ws_take(nb * numel) : nullptr;
     if (!part && nb > 16) nb = 16;
     const dim3 grid((unsigned)nb);
-#define LEDN_C1(TX, TZ)                                                                                       \
-    do {                                                                                                      \
-        if (d.KH == 3) LEDN_LAUNCH((conv_wgrad_cin1_kernel<TX, TZ, 3>), grid, dim3(256), 0, s, d, part);      \
-        else LEDN_LAUNCH((conv_wgrad_cin1_kernel<TX, TZ, 1>), grid, dim3(256), 0, s, d, part);                \
-    } while (0)
-    if (d.dtype_x == LEDN_F32 && d.dtype_dz == LEDN_F32) LEDN_C1(float, float);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_dz == LEDN_BF16) LEDN_C1(bf16_t, bf16_t);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_dz == LEDN_F32) LEDN_C1(bf16_t, float);
-    else if (d.dtype_x == LEDN_F32 && d.dtype_dz == LEDN_BF16) LEDN_C1(float, bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_C1
-    int rc = part ? finish_partials(part, (int)nb, (int)numel, 1, d.dw, nullptr, nullptr, s) : check_launch();
+    int rc = with_dtypes(d.dtype_x, d.dtype_dz, [&](auto tx, auto tz) {
+        using TX = tag_t<decltype(tx)>;
+        using TZ = tag_t<decltype(tz)>;
+        if (d.KH == 3) LEDN_LAUNCH((conv_wgrad_cin1_kernel<TX, TZ, 3>), grid, dim3(256), 0, s, d, part);
+        else LEDN_LAUNCH((conv_wgrad_cin1_kernel<TX, TZ, 1>), grid, dim3(256), 0, s, d, part);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
+    rc = part ? finish_partials(part, (int)nb, (int)numel, 1, d.dw, nullptr, nullptr, s) : check_launch();
     if (rc != LEDN_OK || !d.db) return rc;
     return channel_stats_impl(d.dz, nullptr, npix, d.Cout, d.dtype_dz, d.db, nullptr, s);
 }
@@ -890,12 +880,9 @@ static int conv_wgrad_cin1(const ledn_wgrad_desc& d, hipStream_t s) {
 int conv_wgrad_direct(const ledn_wgrad_desc& d, hipStream_t s) {
     if (cin1_ok(d) && (options().stream_fast & 2)) return conv_wgrad_cin1(d, s);
     if (narrow_ok(d)) {
-        int rc;
-        if (d.dtype_x == LEDN_F32 && d.dtype_dz == LEDN_F32) rc = launch_narrow<float, float>(d, s);
-        else if (d.dtype_x == LEDN_BF16 && d.dtype_dz == LEDN_BF16) rc = launch_narrow<bf16_t, bf16_t>(d, s);
-        else if (d.dtype_x == LEDN_BF16 && d.dtype_dz == LEDN_F32) rc = launch_narrow<bf16_t, float>(d, s);
-        else if (d.dtype_x == LEDN_F32 && d.dtype_dz == LEDN_BF16) rc = launch_narrow<float, bf16_t>(d, s);
-        else return LEDN_EINVAL;
+        const int rc = with_dtypes(d.dtype_x, d.dtype_dz, [&](auto tx, auto tz) {
+            return launch_narrow<tag_t<decltype(tx)>, tag_t<decltype(tz)>>(d, s);
+        });
         if (rc != LEDN_OK || !d.db) return rc;
         return channel_stats_impl(d.dz, nullptr, (long long)d.N * d.Ho * d.Wo, d.Cout, d.dtype_dz, d.db, nullptr, s);
     }
@@ -913,15 +900,13 @@ int conv_wgrad_direct(const ledn_wgrad_desc& d, hipStream_t s) {
     long ppb = cdiv(cdiv(npix, nbx), WG_PC) * WG_PC;
     nbx = cdiv(npix, ppb);
     const dim3 grid((unsigned)nbx, (unsigned)(ci_tiles * co_tiles * d.groups), (unsigned)(d.KH * d.KW));
-#define LEDN_WG(TX, TZ) \
-    LEDN_LAUNCH((conv_wgrad_direct_kernel<TX, TZ>), grid, dim3(256), 0, s, d, (int)ppb, ci_tiles, co_tiles, part, numel)
-    if (d.dtype_x == LEDN_F32 && d.dtype_dz == LEDN_F32) LEDN_WG(float, float);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_dz == LEDN_BF16) LEDN_WG(bf16_t, bf16_t);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_dz == LEDN_F32) LEDN_WG(bf16_t, float);
-    else if (d.dtype_x == LEDN_F32 && d.dtype_dz == LEDN_BF16) LEDN_WG(float, bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_WG
-    int rc = part ? finish_partials(part, (int)nbx, (int)numel, 1, d.dw, nullptr, nullptr, s) : check_launch();
+    int rc = with_dtypes(d.dtype_x, d.dtype_dz, [&](auto tx, auto tz) {
+        LEDN_LAUNCH((conv_wgrad_direct_kernel<tag_t<decltype(tx)>, tag_t<decltype(tz)>>), grid, dim3(256), 0, s, d, (int)ppb,
+                    ci_tiles, co_tiles, part, numel);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
+    rc = part ? finish_partials(part, (int)nbx, (int)numel, 1, d.dw, nullptr, nullptr, s) : check_launch();
     if (rc != LEDN_OK) return rc;
     if (d.db) rc = channel_stats_impl(d.dz, nullptr, npix, d.Cout, d.dtype_dz, d.db, nullptr, s);
     return rc;

@@ -1090,16 +1090,13 @@ int stem_conv_impl(const void* x, int dtype_x, const void* wp, void* y, int N, i
     const long ntiles = (long)N * cdiv(Ho, 4) * cdiv(Wo, 64);
     long nb = ntiles < 2048 ? ntiles : 2048;      // (one-shot workgroups measured slower: 198 vs 182 us)
     a.part = (stat_sum && (nb > 16 || det())) ? ws_take(nb * 64) : nullptr;
-#define LEDN_STEM(TX)                                                                                      \
-    do {                                                                                                   \
-        if (full) LEDN_LAUNCH((stem_conv_kernel<TX, true>), dim3((unsigned)nb), dim3(256), 0, s, a);       \
-        else LEDN_LAUNCH((stem_conv_kernel<TX, false>), dim3((unsigned)nb), dim3(256), 0, s, a);           \
-    } while (0)
-    if (dtype_x == LEDN_U8) LEDN_STEM(unsigned char);
-    else if (dtype_x == LEDN_F32) LEDN_STEM(float);
-    else if (dtype_x == LEDN_BF16) LEDN_STEM(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_STEM
+    const int rc = with_dtype_u8(dtype_x, [&](auto tx) {
+        using TX = tag_t<decltype(tx)>;
+        if (full) LEDN_LAUNCH((stem_conv_kernel<TX, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+        else LEDN_LAUNCH((stem_conv_kernel<TX, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     if (a.part) return finish_partials(a.part, (int)nb, 32, 2, stat_sum, stat_sqsum, nullptr, s);
     return check_launch();
 }
@@ -1111,22 +1108,17 @@ int im2col_stem_planar_impl(const void* x, int dtype_x, void* p, int N, int H, i
     LEDN_REQUIRE(Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1);
     LEDN_REQUIRE((scale == nullptr) == (shift == nullptr));
     const dim3 grid((unsigned)((long)N * Ho * cdiv(Wo, 64)));
-#define LEDN_IPC(TX, CC)                                                                                    \
-    LEDN_LAUNCH((im2col_stem_planar_kernel<TX, CC>), grid, dim3(256), 0, s, (const TX*)x, (bf16_t*)p, N, H, W, Ho, \
-                Wo, scale, shift, map, valid_hw, pad_val)
-#define LEDN_IP(TX)                  \
-    do {                             \
-        if (C == 3) LEDN_IPC(TX, 3); \
-        else if (C == 2) LEDN_IPC(TX, 2); \
-        else LEDN_IPC(TX, 1);        \
-    } while (0)
-    if (dtype_x == LEDN_U8) LEDN_IP(unsigned char);
-    else if (dtype_x == LEDN_F32) LEDN_IP(float);
-    else if (dtype_x == LEDN_BF16) LEDN_IP(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_IP
+    return with_dtype_u8(dtype_x, [&](auto tx) {
+        using TX = tag_t<decltype(tx)>;
+#define LEDN_IPC(CC)                                                                                                   \
+    LEDN_LAUNCH((im2col_stem_planar_kernel<TX, CC>), grid, dim3(256), 0, s, (const TX*)x, (bf16_t*)p, N, H, W, Ho, Wo, \
+                scale, shift, map, valid_hw, pad_val)
+        if (C == 3) LEDN_IPC(3);
+        else if (C == 2) LEDN_IPC(2);
+        else LEDN_IPC(1);
 #undef LEDN_IPC
-    return check_launch();
+        return check_launch();
+    });
 }
 
 int im2col_stem_impl(const void* x, void* p, int N, int H, int W, int C, int Ho, int Wo, hipStream_t s) {

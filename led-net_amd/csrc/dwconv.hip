@@ -979,18 +979,15 @@ int dwconv_impl(const ledn_dw_desc& d, hipStream_t s) {
     }
     const dim3 grid((unsigned)nb);
     const bool k3 = d.KH == 3 && d.KW == 3;
-#define LEDN_DW(TX, TY)                                                                          \
-    do {                                                                                         \
-        if (v4 && k3) LEDN_LAUNCH((dwconv_kernel<TX, TY, 4, 9>), grid, dim3(256), 0, s, d, part); \
-        else if (v4) LEDN_LAUNCH((dwconv_kernel<TX, TY, 4, 0>), grid, dim3(256), 0, s, d, part);  \
-        else LEDN_LAUNCH((dwconv_kernel<TX, TY, 1, 0>), grid, dim3(256), 0, s, d, part);          \
-    } while (0)
-    if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_F32) LEDN_DW(float, float);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_BF16) LEDN_DW(bf16_t, bf16_t);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_F32) LEDN_DW(bf16_t, float);
-    else if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_BF16) LEDN_DW(float, bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_DW
+    const int rc = with_dtypes(d.dtype_x, d.dtype_y, [&](auto tx, auto ty) {
+        using TX = tag_t<decltype(tx)>;
+        using TY = tag_t<decltype(ty)>;
+        if (v4 && k3) LEDN_LAUNCH((dwconv_kernel<TX, TY, 4, 9>), grid, dim3(256), 0, s, d, part);
+        else if (v4) LEDN_LAUNCH((dwconv_kernel<TX, TY, 4, 0>), grid, dim3(256), 0, s, d, part);
+        else LEDN_LAUNCH((dwconv_kernel<TX, TY, 1, 0>), grid, dim3(256), 0, s, d, part);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     if (part) return finish_partials(part, (int)nb, d.C, 2, d.stat_sum, d.stat_sqsum, nullptr, s);
     return check_launch();
 }
@@ -1043,16 +1040,13 @@ int sesp_pyramid_impl(const ledn_pyr_desc& d, hipStream_t s) {
     const bool v4 = d.n % 4 == 0;
     const long total = (long)d.N * d.Ho * d.Wo * (v4 ? d.n / 4 : d.n);
     const dim3 grid((unsigned)cdiv(total, 256));
-#define LEDN_PY(TX, TY)                                                                   \
-    do {                                                                                  \
-        if (v4) LEDN_LAUNCH((sesp_pyramid_kernel<TX, TY, 4>), grid, dim3(256), 0, s, d);  \
-        else LEDN_LAUNCH((sesp_pyramid_kernel<TX, TY, 1>), grid, dim3(256), 0, s, d);     \
-    } while (0)
-    if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_F32) LEDN_PY(float, float);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_BF16) LEDN_PY(bf16_t, bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_PY
-    return check_launch();
+    LEDN_REQUIRE(d.dtype_y == d.dtype_x);   // no mixed-dtype pyramid kernel
+    return with_dtype(d.dtype_x, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4) LEDN_LAUNCH((sesp_pyramid_kernel<T, T, 4>), grid, dim3(256), 0, s, d);
+        else LEDN_LAUNCH((sesp_pyramid_kernel<T, T, 1>), grid, dim3(256), 0, s, d);
+        return check_launch();
+    });
 }
 
 // ---------------------------------------------------------------------------

@@ -205,22 +205,17 @@ int window_attn_impl(const void* qkv, const float* biasT, void* out, int N, int 
         return check_launch();
     }
     const dim3 grid((unsigned)(N * hh * ww), (unsigned)heads);
-#define LEDN_WA(T, DD)                                                                          \
-    LEDN_LAUNCH((window_attn_kernel<T, DD>), grid, dim3(64), 0, s, (const T*)qkv, biasT, (T*)out, N, H, \
-                W, C, heads, hh, ww)
-#define LEDN_WAD(T)                    \
-    do {                               \
-        if (D == 8) LEDN_WA(T, 8);     \
-        else if (D == 16) LEDN_WA(T, 16); \
-        else if (D == 32) LEDN_WA(T, 32); \
-        else return LEDN_EINVAL;       \
-    } while (0)
-    if (dtype == LEDN_F32) LEDN_WAD(float);
-    else if (dtype == LEDN_BF16) LEDN_WAD(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_WAD
+    return with_dtype(dtype, [&](auto t) -> int {
+        using T = tag_t<decltype(t)>;
+#define LEDN_WA(DD) \
+    LEDN_LAUNCH((window_attn_kernel<T, DD>), grid, dim3(64), 0, s, (const T*)qkv, biasT, (T*)out, N, H, W, C, heads, hh, ww)
+        if (D == 8) LEDN_WA(8);
+        else if (D == 16) LEDN_WA(16);
+        else if (D == 32) LEDN_WA(32);
+        else return LEDN_EINVAL;
 #undef LEDN_WA
-    return check_launch();
+        return check_launch();
+    });
 }
 
 // out[y,x] = 1/ws * sum_{i<ws} P(y-ws/2+1+i, x) + 1/ws * sum_{i<ws} Q(y, x-ws/2+1+i) + local
@@ -272,14 +267,11 @@ int getb_pool_impl(const void* a, const void* local, void* out, int N, int H, in
     LEDN_REQUIRE(a && local && out && N > 0 && H >= 2 && W >= 2 && C > 0 && ws >= 2 && C % 4 == 0);
     const long total = (long)N * H * W * (C / 4);
     const dim3 grid((unsigned)cdiv(total, 256));
-    if (dtype == LEDN_F32)
-        LEDN_LAUNCH((getb_pool_kernel<float, 4>), grid, dim3(256), 0, s, (const float*)a,
-                    (const float*)local, (float*)out, N, H, W, C, ws);
-    else if (dtype == LEDN_BF16)
-        LEDN_LAUNCH((getb_pool_kernel<bf16_t, 4>), grid, dim3(256), 0, s, (const bf16_t*)a,
-                    (const bf16_t*)local, (bf16_t*)out, N, H, W, C, ws);
-    else return LEDN_EINVAL;
-    return check_launch();
+    return with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        LEDN_LAUNCH((getb_pool_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)a, (const T*)local, (T*)out, N, H, W, C, ws);
+        return check_launch();
+    });
 }
 
 // ---------------------------------------------------------------------------

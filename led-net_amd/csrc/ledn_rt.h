@@ -5,6 +5,7 @@
 // header.  Wave = 64 lanes everywhere.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 
 #ifdef LEDN_CPU_EMU
 #include "emu.h"
@@ -406,6 +407,25 @@ inline int check_launch() {
     return e == hipSuccess ? LEDN_OK : LEDN_ELAUNCH;
 }
 __host__ __device__ inline long cdiv(long a, long b) { return (a + b - 1) / b; }
+
+// Dtype dispatch of the launchers: with_dtype(code, f) calls f(type_tag<T>{}) with the storage type of a LEDN_* dtype code
+// and returns its result; any other code returns LEDN_EINVAL without calling f.  In the (generic) lambda,
+// `using T = tag_t<decltype(t)>;` names the type.  A launcher whose kernels exist for a subset of the combinations
+// rejects the rest with an `if constexpr` on the types.
+template <class T> struct type_tag { using type = T; };
+template <class Tag> using tag_t = typename Tag::type;
+template <class F> inline int with_dtype(int dt, F&& f) {
+    if (dt == LEDN_F32) return f(type_tag<float>{});
+    if (dt == LEDN_BF16) return f(type_tag<bf16_t>{});
+    return LEDN_EINVAL;
+}
+template <class F> inline int with_dtypes(int dx, int dy, F&& f) {
+    return with_dtype(dx, [&](auto tx) { return with_dtype(dy, [&](auto ty) { return f(tx, ty); }); });
+}
+// the stem / input kernels also read 8-bit images
+template <class F> inline int with_dtype_u8(int dt, F&& f) {
+    return dt == LEDN_U8 ? f(type_tag<unsigned char>{}) : with_dtype(dt, f);
+}
 
 // Caller-provided scratch (ledn_set_workspace): cross-workgroup reductions write per-workgroup
 // partials here and a tiny second kernel sums them -- no same-address atomics (which serialise

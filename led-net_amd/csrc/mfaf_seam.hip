@@ -137,10 +137,10 @@ int mfaf_gate_impl(const ledn_mfaf_desc& d, hipStream_t s) {
     }
     const long total = (long)d.N * d.H * d.W * (d.C / 4);
     const dim3 grid((unsigned)cdiv(total, 256));
-    if (d.dtype == LEDN_F32) LEDN_LAUNCH((mfaf_gate_kernel<float, 4>), grid, dim3(256), 0, s, d);
-    else if (d.dtype == LEDN_BF16) LEDN_LAUNCH((mfaf_gate_kernel<bf16_t, 4>), grid, dim3(256), 0, s, d);
-    else return LEDN_EINVAL;
-    return check_launch();
+    return with_dtype(d.dtype, [&](auto t) {
+        LEDN_LAUNCH((mfaf_gate_kernel<tag_t<decltype(t)>, 4>), grid, dim3(256), 0, s, d);
+        return check_launch();
+    });
 }
 
 // ---------------------------------------------------------------------------

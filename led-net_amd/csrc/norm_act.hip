@@ -136,22 +136,17 @@ int channel_stats_impl(const void* x, const void* xadd, long long P, int C, int 
     if (nb > 64 || det()) part = ws_take(nb * 2 * C);
     if (!part && nb > 256) nb = 256;     // atomics fallback: one per channel per workgroup, bounded grid
     const dim3 grid((unsigned)nb);
-#define LEDN_CS(T)                                                                              \
-    do {                                                                                        \
-        if (V == 8)                                                                             \
-            LEDN_LAUNCH((channel_stats_kernel<T, 8>), grid, dim3(256), 0, s, (const T*)x,       \
-                        (const T*)xadd, (long)P, C, sum, sqsum, part);                      \
-        else if (V == 4)                                                                        \
-            LEDN_LAUNCH((channel_stats_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)x,       \
-                        (const T*)xadd, (long)P, C, sum, sqsum, part);                      \
-        else                                                                                    \
-            LEDN_LAUNCH((channel_stats_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x,       \
-                        (const T*)xadd, (long)P, C, sum, sqsum, part);                      \
-    } while (0)
-    if (dtype == LEDN_F32) LEDN_CS(float);
-    else if (dtype == LEDN_BF16) LEDN_CS(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_CS
+    const int rc = with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (V == 4)
+            LEDN_LAUNCH((channel_stats_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)x, (const T*)xadd, (long)P, C, sum,
+                        sqsum, part);
+        else
+            LEDN_LAUNCH((channel_stats_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x, (const T*)xadd, (long)P, C, sum,
+                        sqsum, part);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     if (part) return finish_partials(part, (int)nb, C, 2, sum, sqsum, nullptr, s);
     return check_launch();
 }
@@ -230,26 +225,19 @@ int affine_act_impl(const ledn_affine_desc& d, hipStream_t s) {
         if (rc >= 0) return rc;
     }
     LEDN_REQUIRE(!d.stat_sum);      // output statistics: the streaming kernel only (include/ledn.h)
-    const bool v4 = d.C % 4 == 0;
-    const bool v8 = false;   // 16 B per lane measured slower than 8 B per lane (see channel_stats_impl)
-    const int cvn = v8 ? d.C / 8 : (v4 ? d.C / 4 : d.C);
+    const bool v4 = d.C % 4 == 0;   // 16 B per lane measured slower than 8 B per lane (see channel_stats_impl)
+    const int cvn = v4 ? d.C / 4 : d.C;
     LEDN_REQUIRE(cvn <= 256);
     long nb = cdiv(d.P, (256 / cvn) * 4);
     if (nb > 4096) nb = 4096;
     const dim3 grid((unsigned)nb);
-#define LEDN_AF(TX, TY)                                                                  \
-    do {                                                                                 \
-        if (v4) LEDN_LAUNCH((affine_act_kernel<TX, TY, 4>), grid, dim3(256), 0, s, d);   \
-        else LEDN_LAUNCH((affine_act_kernel<TX, TY, 1>), grid, dim3(256), 0, s, d);      \
-    } while (0)
-    if (v8) LEDN_LAUNCH((affine_act_kernel<bf16_t, bf16_t, 8>), grid, dim3(256), 0, s, d);
-    else if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_F32) LEDN_AF(float, float);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_BF16) LEDN_AF(bf16_t, bf16_t);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_F32) LEDN_AF(bf16_t, float);
-    else if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_BF16) LEDN_AF(float, bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_AF
-    return check_launch();
+    return with_dtypes(d.dtype_x, d.dtype_y, [&](auto tx, auto ty) {
+        using TX = tag_t<decltype(tx)>;
+        using TY = tag_t<decltype(ty)>;
+        if (v4) LEDN_LAUNCH((affine_act_kernel<TX, TY, 4>), grid, dim3(256), 0, s, d);
+        else LEDN_LAUNCH((affine_act_kernel<TX, TY, 1>), grid, dim3(256), 0, s, d);
+        return check_launch();
+    });
 }
 
 // ---- planar (NCHW) -> interleaved (NHWC) with per-channel affine and channel map
@@ -280,17 +268,19 @@ int nchw_to_nhwc_impl(const void* x, int dtype_x, void* y, int dtype_y, int N, i
     LEDN_REQUIRE(x && y && N > 0 && C > 0 && H > 0 && W > 0);
     LEDN_REQUIRE((scale == nullptr) == (shift == nullptr));
     const dim3 grid((unsigned)cdiv((long)N * H * W, 256));
-#define LEDN_L(TX, TY) \
-    LEDN_LAUNCH((nchw_to_nhwc_kernel<TX, TY>), grid, dim3(256), 0, s, (const TX*)x, (TY*)y, N, C, H, W, scale, shift, map, \
-                valid_hw, pad_val)
-    if (dtype_x == LEDN_F32 && dtype_y == LEDN_F32) LEDN_L(float, float);
-    else if (dtype_x == LEDN_F32 && dtype_y == LEDN_BF16) LEDN_L(float, bf16_t);
-    else if (dtype_x == LEDN_BF16 && dtype_y == LEDN_BF16) LEDN_L(bf16_t, bf16_t);
-    else if (dtype_x == LEDN_U8 && dtype_y == LEDN_F32) LEDN_L(unsigned char, float);
-    else if (dtype_x == LEDN_U8 && dtype_y == LEDN_BF16) LEDN_L(unsigned char, bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_L
-    return check_launch();
+    return with_dtype_u8(dtype_x, [&](auto tx) {
+        return with_dtype(dtype_y, [&](auto ty) {
+            using TX = tag_t<decltype(tx)>;
+            using TY = tag_t<decltype(ty)>;
+            if constexpr (std::is_same_v<TX, bf16_t> && std::is_same_v<TY, float>) {
+                return LEDN_EINVAL;   // no bf16 -> f32 kernel
+            } else {
+                LEDN_LAUNCH((nchw_to_nhwc_kernel<TX, TY>), grid, dim3(256), 0, s, (const TX*)x, (TY*)y, N, C, H, W, scale,
+                            shift, map, valid_hw, pad_val);
+                return check_launch();
+            }
+        });
+    });
 }
 
 // BatchNorm finalize straight from the producer's per-workgroup statistic rows part[rows][2][C]

@@ -73,41 +73,36 @@ int bilinear_impl(const ledn_resize_desc& d, hipStream_t s) {
     if (d.out_nchw) {
         LEDN_REQUIRE(d.dtype_y == LEDN_F32);
         const dim3 grid((unsigned)cdiv((long)d.N * d.Ho * d.Wo, 256));
-#define LEDN_BN(C)                                                                               \
-    do {                                                                                         \
-        if (d.dtype_x == LEDN_F32) LEDN_LAUNCH((bilinear_nchw_kernel<float, C>), grid, dim3(256), 0, s, d);  \
-        else LEDN_LAUNCH((bilinear_nchw_kernel<bf16_t, C>), grid, dim3(256), 0, s, d);           \
-    } while (0)
-        switch (d.C) {
-            case 1: LEDN_BN(1); break;
-            case 2: LEDN_BN(2); break;
-            case 3: LEDN_BN(3); break;
-            case 4: LEDN_BN(4); break;
-            case 5: LEDN_BN(5); break;
-            case 8: LEDN_BN(8); break;
-            case 19: LEDN_BN(19); break;
-            default: return LEDN_EINVAL;
-        }
+        return with_dtype(d.dtype_x, [&](auto tx) -> int {
+            using TX = tag_t<decltype(tx)>;
+#define LEDN_BN(C) \
+    case C: LEDN_LAUNCH((bilinear_nchw_kernel<TX, C>), grid, dim3(256), 0, s, d); break
+            switch (d.C) {
+                LEDN_BN(1);
+                LEDN_BN(2);
+                LEDN_BN(3);
+                LEDN_BN(4);
+                LEDN_BN(5);
+                LEDN_BN(8);
+                LEDN_BN(19);
+                default: return LEDN_EINVAL;
+            }
 #undef LEDN_BN
-        return check_launch();
+            return check_launch();
+        });
     }
     LEDN_REQUIRE(d.argmax == nullptr);
     const bool v4 = d.C % 4 == 0, v2 = d.C % 2 == 0;    // v2: the 2-class logit pyramid (one access per pixel)
     const long total = (long)d.N * d.Ho * d.Wo * (v4 ? d.C / 4 : (v2 ? d.C / 2 : d.C));
     const dim3 grid((unsigned)cdiv(total, 256));
-#define LEDN_BL(TX, TY)                                                                    \
-    do {                                                                                   \
-        if (v4) LEDN_LAUNCH((bilinear_nhwc_kernel<TX, TY, 4>), grid, dim3(256), 0, s, d);  \
-        else if (v2) LEDN_LAUNCH((bilinear_nhwc_kernel<TX, TY, 2>), grid, dim3(256), 0, s, d);  \
-        else LEDN_LAUNCH((bilinear_nhwc_kernel<TX, TY, 1>), grid, dim3(256), 0, s, d);     \
-    } while (0)
-    if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_F32) LEDN_BL(float, float);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_BF16) LEDN_BL(bf16_t, bf16_t);
-    else if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_F32) LEDN_BL(bf16_t, float);
-    else if (d.dtype_x == LEDN_F32 && d.dtype_y == LEDN_BF16) LEDN_BL(float, bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_BL
-    return check_launch();
+    return with_dtypes(d.dtype_x, d.dtype_y, [&](auto tx, auto ty) {
+        using TX = tag_t<decltype(tx)>;
+        using TY = tag_t<decltype(ty)>;
+        if (v4) LEDN_LAUNCH((bilinear_nhwc_kernel<TX, TY, 4>), grid, dim3(256), 0, s, d);
+        else if (v2) LEDN_LAUNCH((bilinear_nhwc_kernel<TX, TY, 2>), grid, dim3(256), 0, s, d);
+        else LEDN_LAUNCH((bilinear_nhwc_kernel<TX, TY, 1>), grid, dim3(256), 0, s, d);
+        return check_launch();
+    });
 }
 
 // ---- adaptive average pool to S x S (PyTorch window: [floor(i*H/S), ceil((i+1)*H/S)) )
@@ -181,19 +176,17 @@ int adaptive_avgpool_impl(const void* x, const void* xadd, float* y, int N, int 
     if (hipMemsetAsync(y, 0, sizeof(float) * (size_t)N * S * S * C, s) != hipSuccess) return LEDN_ELAUNCH;
     // <= 256 chunk rows: finish_partials adds each output's row sums in one thread group, in row order
     float* part = (grid.y > 1 && grid.y <= 256) ? ws_take((long)grid.y * N * S * S * C) : nullptr;
-#define LEDN_AA(T)                                                                                    \
-    do {                                                                                              \
-        if (V == 4)                                                                                   \
-            LEDN_LAUNCH((adaptive_avgpool_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)x,          \
-                        (const T*)xadd, y, N, H, W, C, S, rpb, part);                                 \
-        else                                                                                          \
-            LEDN_LAUNCH((adaptive_avgpool_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x,          \
-                        (const T*)xadd, y, N, H, W, C, S, rpb, part);                                 \
-    } while (0)
-    if (dtype == LEDN_F32) LEDN_AA(float);
-    else if (dtype == LEDN_BF16) LEDN_AA(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_AA
+    const int rc = with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (V == 4)
+            LEDN_LAUNCH((adaptive_avgpool_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)x, (const T*)xadd, y, N, H, W, C,
+                        S, rpb, part);
+        else
+            LEDN_LAUNCH((adaptive_avgpool_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x, (const T*)xadd, y, N, H, W, C,
+                        S, rpb, part);
+        return LEDN_OK;
+    });
+    if (rc != LEDN_OK) return rc;
     if (part) return finish_partials(part, (int)grid.y, N * S * S * C, 1, y, nullptr, nullptr, s);
     return check_launch();
 }
@@ -237,16 +230,12 @@ int avgpool3x3s2_impl(const void* x, void* y, int N, int H, int W, int C, int Ho
     const bool v4 = C % 4 == 0;
     const long total = (long)N * Ho * Wo * (v4 ? C / 4 : C);
     const dim3 grid((unsigned)cdiv(total, 256));
-#define LEDN_AP(T)                                                                                 \
-    do {                                                                                           \
-        if (v4) LEDN_LAUNCH((avgpool3x3s2_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, Ho, Wo); \
-        else LEDN_LAUNCH((avgpool3x3s2_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, Ho, Wo);    \
-    } while (0)
-    if (dtype == LEDN_F32) LEDN_AP(float);
-    else if (dtype == LEDN_BF16) LEDN_AP(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_AP
-    return check_launch();
+    return with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4) LEDN_LAUNCH((avgpool3x3s2_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, Ho, Wo);
+        else LEDN_LAUNCH((avgpool3x3s2_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, Ho, Wo);
+        return check_launch();
+    });
 }
 
 // ---- k x k / stride s / pad p average pool, zero padding counted in the divisor (nn.AvgPool2d defaults:
@@ -287,16 +276,12 @@ int avgpool2d_impl(const void* x, void* y, int N, int H, int W, int C, int Ho, i
     const bool v4 = C % 4 == 0;
     const long total = (long)N * Ho * Wo * (v4 ? C / 4 : C);
     const dim3 grid((unsigned)cdiv(total, 256));
-#define LEDN_AP(T)                                                                                          \
-    do {                                                                                                    \
-        if (v4) LEDN_LAUNCH((avgpool2d_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, Ho, Wo, k, st, pad); \
-        else LEDN_LAUNCH((avgpool2d_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, Ho, Wo, k, st, pad);    \
-    } while (0)
-    if (dtype == LEDN_F32) LEDN_AP(float);
-    else if (dtype == LEDN_BF16) LEDN_AP(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_AP
-    return check_launch();
+    return with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4) LEDN_LAUNCH((avgpool2d_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, Ho, Wo, k, st, pad);
+        else LEDN_LAUNCH((avgpool2d_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, Ho, Wo, k, st, pad);
+        return check_launch();
+    });
 }
 
 // adjoint in gather form: dx[y,x] = 1/k^2 * sum of dy over the windows that contain (y,x)
@@ -337,16 +322,12 @@ int avgpool2d_bwd_impl(const void* dy, void* dx, int N, int H, int W, int C, int
     const bool v4 = C % 4 == 0;
     const long total = (long)N * H * W * (v4 ? C / 4 : C);
     const dim3 grid((unsigned)cdiv(total, 256));
-#define LEDN_AP(T)                                                                                          \
-    do {                                                                                                    \
-        if (v4) LEDN_LAUNCH((avgpool2d_bwd_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, k, st, pad); \
-        else LEDN_LAUNCH((avgpool2d_bwd_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, k, st, pad);    \
-    } while (0)
-    if (dtype == LEDN_F32) LEDN_AP(float);
-    else if (dtype == LEDN_BF16) LEDN_AP(bf16_t);
-    else return LEDN_EINVAL;
-#undef LEDN_AP
-    return check_launch();
+    return with_dtype(dtype, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if (v4) LEDN_LAUNCH((avgpool2d_bwd_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, k, st, pad);
+        else LEDN_LAUNCH((avgpool2d_bwd_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, k, st, pad);
+        return check_launch();
+    });
 }
 
 // ---------------------------------------------------------------------------

@@ -702,7 +702,6 @@ int bn_act_bwd_fused(const ledn_bnbwd_desc& d, hipStream_t s) {
     if (d.act == LEDN_ACT_SIGMOID || d.act == LEDN_ACT_RELU6 || d.res_mode == LEDN_RES_GATE) return LEDN_ESKIP;
     const bool has_dres = d.dres != nullptr;
     if (has_dres && d.res_mode == LEDN_RES_NONE) return LEDN_ESKIP;
-    if (!d.bn_mode && d.slope == nullptr && false) return LEDN_ESKIP;
     const long nvec = d.P * d.C / 8;
     static const long vmin = exp_knob("LEDN_BNF_MIN", 1L << 16);
     if (nvec < vmin || nvec > (long)BF_G * BF_T * 16) return LEDN_ESKIP;
