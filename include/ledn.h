@@ -270,6 +270,31 @@ typedef struct {
     int dtype_x, dtype_y;
 } ledn_dw_desc;
 int ledn_dwconv2d(const ledn_dw_desc* d, void* stream);
+/* "Which kernel" queries of the depthwise and pyramid entries: ledn_X_kernel_id(d, stream) takes the descriptor and stream
+ * ledn_X would be called with, launches nothing, touches no device memory, and returns the kernel instance ledn_X would
+ * run under the current options (ledn_set_option), deterministic mode and the workspace bound to `stream` -- decided by
+ * the very functions the launcher asks (csrc: *_plan).  -1: ledn_X would return LEDN_EINVAL.  For the entries whose kernel
+ * ends in a cross-workgroup f32 reduction (forward statistics, weight gradients) the ending is OR-ed in:
+ *   LEDN_END_ATOMIC   one atomicAdd per element and workgroup,
+ *   LEDN_END_PARTIAL  one partial row per workgroup (or tile) in the workspace, summed in a fixed order by a second launch;
+ * (value & LEDN_KERNEL_MASK) is the instance, 0 in the ending bits = no reduction (forward without stat_sum).
+ * The storage types TX / TY of a templated instance are the descriptor's dtype fields and are not part of the value. */
+enum { LEDN_KERNEL_MASK = 0xff, LEDN_END_ATOMIC = 0x100, LEDN_END_PARTIAL = 0x200 };
+/* ledn_dwconv2d (csrc/dwconv.hip).  The two <.,2,8> tile instances are reachable only through the LEDN_DW_TH A/B knob
+ * (LEDN_EXPERIMENTAL, read once per process). */
+enum {
+    LEDN_DW_GENERIC_V1 = 0,       /* dwconv_kernel<TX,TY,1,0>: C or group_size not a multiple of 4 */
+    LEDN_DW_GENERIC_V4 = 1,       /* dwconv_kernel<TX,TY,4,0>: any filter but 3x3 */
+    LEDN_DW_GENERIC_V4_3X3 = 2,   /* dwconv_kernel<TX,TY,4,9> */
+    LEDN_DW_BF16 = 3,             /* dw3x3_bf16_kernel<0> */
+    LEDN_DW_TILE_2_16_PLAIN = 4,  /* dw3x3_tile_kernel<0,2,16,false>: no epilogue (the training forward) */
+    LEDN_DW_TILE_2_16 = 5,        /* dw3x3_tile_kernel<0,2,16> */
+    LEDN_DW_TILE_2_8 = 6,         /* dw3x3_tile_kernel<0,2,8> */
+    LEDN_DW_TILE_5_8_PLAIN = 7,   /* dw3x3_tile_kernel<0,5,8,false> */
+    LEDN_DW_TILE_5_8 = 8,         /* dw3x3_tile_kernel<0,5,8> */
+    LEDN_DW_TILE8X8 = 9           /* dw8x8_tile_kernel<0> */
+};
+int ledn_dwconv2d_kernel_id(const ledn_dw_desc* d, void* stream);
 
 /* Layout bridge between PyTorch's depthwise filters [n_k][1][KH][KW] (the state_dict layout of
  * CDilated.conv.weight, nn_layers/espnet_utils.py:120-142, and SeparableConvBN's depthwise,
@@ -344,6 +369,14 @@ typedef struct {
     int dtype_x, dtype_y;
 } ledn_pyr_desc;
 int ledn_sesp_pyramid(const ledn_pyr_desc* d, void* stream);
+/* which kernel ledn_sesp_pyramid runs d on (see ledn_dwconv2d_kernel_id; no reduction, so no ending bits) */
+enum {
+    LEDN_PYR_GENERIC_V1 = 0,      /* sesp_pyramid_kernel<T,T,1>: n not a multiple of 4 */
+    LEDN_PYR_GENERIC_V4 = 1,      /* sesp_pyramid_kernel<T,T,4> */
+    LEDN_PYR_BF16 = 2,            /* pyr_fwd_bf16_kernel<false> */
+    LEDN_PYR_BF16_SAME = 3        /* pyr_fwd_bf16_kernel<true>: four equal dilations */
+};
+int ledn_sesp_pyramid_kernel_id(const ledn_pyr_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Per-channel statistics and elementwise affine / activation.
@@ -676,6 +709,28 @@ typedef struct {
 } ledn_dwbwd_desc;
 int ledn_dwconv2d_bwd_data(const ledn_dwbwd_desc* d, void* stream);
 int ledn_dwconv2d_bwd_weight(const ledn_dwbwd_desc* d, void* stream);
+/* which kernel the two entries run d on (see ledn_dwconv2d_kernel_id).  The data gradient has no reduction; the weight
+ * gradient's value carries LEDN_END_ATOMIC or LEDN_END_PARTIAL.  ledn_dwconv2d_bwd_data_kernel_id needs w and dx set,
+ * ledn_dwconv2d_bwd_weight_kernel_id x and dw (tested for NULL only). */
+enum {
+    LEDN_DWBD_GENERIC_V1 = 0,     /* dw_bwd_data_kernel<T,1> */
+    LEDN_DWBD_GENERIC_V4 = 1,     /* dw_bwd_data_kernel<T,4> */
+    LEDN_DWBD_BF16 = 2,           /* dw3x3_bf16_kernel<1> */
+    LEDN_DWBD_TILE_2_16 = 3,      /* dw3x3_tile_kernel<1,2,16> */
+    LEDN_DWBD_TILE_2_8 = 4,       /* dw3x3_tile_kernel<1,2,8> (LEDN_DW_TH A/B knob only) */
+    LEDN_DWBD_TILE_5_8 = 5,       /* dw3x3_tile_kernel<1,5,8> */
+    LEDN_DWBD_TILE8X8 = 6         /* dw8x8_tile_kernel<1> into the workspace, then dw8x8_fold_kernel */
+};
+enum {
+    LEDN_DWBW_TAP_V1 = 0,         /* dw_bwd_weight_kernel<T,1>: a filter tap per workgroup column */
+    LEDN_DWBW_TAP_V4 = 1,         /* dw_bwd_weight_kernel<T,4> */
+    LEDN_DWBW_ROW_V4_KW8 = 2,     /* dw_bwd_weight_row_kernel<T,4,8>: KW = 8, a filter row per workgroup column */
+    LEDN_DWBW_3X3_V4 = 3,         /* dw_bwd_weight3x3_kernel<T,4> */
+    LEDN_DWBW_BF16_3X3 = 4,       /* dw3x3_bwd_weight_bf16_kernel */
+    LEDN_DWBW_TILE8X8 = 5         /* dw8x8_wgrad_tile_kernel (always LEDN_END_PARTIAL: one row per tile) */
+};
+int ledn_dwconv2d_bwd_data_kernel_id(const ledn_dwbwd_desc* d, void* stream);
+int ledn_dwconv2d_bwd_weight_kernel_id(const ledn_dwbwd_desc* d, void* stream);
 /* Both gradients of one descriptor (x, dz, w, dx and dw all set; `add` optional).  When the fused gate holds and
  * LEDN_OPT_STREAM_FAST bit 1 is set and a workspace of LEDN_OPT_DW_BWD_WORKGROUPS * 9 * 32 floats is bound, ONE kernel
  * (dw3x3_bwd_tile_kernel, csrc/dwconv.hip) stages dz once in LDS and forms dx and dw from the same taps, followed by the
@@ -718,6 +773,15 @@ int ledn_sesp_pyramid_bwd_weight(const ledn_pyrbwd_desc* d, void* stream);
  * non-NULL): 0 pyr_bwd_data_kernel, 1 pyr_bwd_data_bf16_kernel (both after pyr_suffix_kernel, gsum written),
  * 2 pyr_bwd_data_tile_kernel, 3 pyr_bwd_data_ctx_kernel (both straight from dy, gsum untouched by either entry point); -1 for a descriptor the entry points reject */
 int ledn_sesp_pyramid_bwd_kernel_id(const ledn_pyrbwd_desc* d);
+/* which kernel ledn_sesp_pyramid_bwd_weight runs d on, with its ending (see ledn_dwconv2d_kernel_id; x, dw and gsum set) */
+enum {
+    LEDN_PYRBW_GENERIC_V1 = 0,    /* pyr_bwd_weight_kernel<T,1> */
+    LEDN_PYRBW_GENERIC_V4 = 1,    /* pyr_bwd_weight_kernel<T,4> */
+    LEDN_PYRBW_BF16 = 2,          /* pyr_bwd_weight_bf16_kernel reading gsum (from_dy = false) */
+    LEDN_PYRBW_BF16_FROM_DY = 3,  /* pyr_bwd_weight_bf16_kernel forming the suffix sums from dy (from_dy = true) */
+    LEDN_PYRBW_SAME = 4           /* pyr_bwd_weight_same_kernel */
+};
+int ledn_sesp_pyramid_bwd_weight_kernel_id(const ledn_pyrbwd_desc* d, void* stream);
 
 /* dx[N,H,W,C] = adjoint of ledn_bilinear (gather form, deterministic); dy [N,Ho,Wo,C]. */
 int ledn_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, int C, int Ho, int Wo,

@@ -201,9 +201,12 @@ _PROTOS = {
     'ledn_dwconv2d_bwd_weight': ([C.POINTER(DwBwdDesc), vp], i32),
     'ledn_dwconv2d_bwd': ([C.POINTER(DwBwdDesc), vp], i32),
     'ledn_dwconv2d_bwd_fused_applies': ([C.POINTER(DwBwdDesc)], i32),
+    'ledn_dwconv2d_bwd_data_kernel_id': ([C.POINTER(DwBwdDesc), vp], i32),
+    'ledn_dwconv2d_bwd_weight_kernel_id': ([C.POINTER(DwBwdDesc), vp], i32),
     'ledn_sesp_pyramid_bwd_data': ([C.POINTER(PyrBwdDesc), vp], i32),
     'ledn_sesp_pyramid_bwd_weight': ([C.POINTER(PyrBwdDesc), vp], i32),
     'ledn_sesp_pyramid_bwd_kernel_id': ([C.POINTER(PyrBwdDesc)], i32),
+    'ledn_sesp_pyramid_bwd_weight_kernel_id': ([C.POINTER(PyrBwdDesc), vp], i32),
     'ledn_bilinear_bwd': ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     'ledn_avgpool3x3s2_bwd': ([vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     'ledn_window_attn_bwd': ([vp, fp, vp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
@@ -289,6 +292,7 @@ _PROTOS = {
     'ledn_pack_conv_weights': ([fp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     'ledn_conv2d_wgrad': ([C.POINTER(WgradDesc), vp], i32),
     'ledn_dwconv2d': ([C.POINTER(DwDesc), vp], i32),
+    'ledn_dwconv2d_kernel_id': ([C.POINTER(DwDesc), vp], i32),
     'ledn_iou_hist': ([vp, vp, i64, i32, i32, fp, vp], i32),
     'ledn_dw_pack': ([C.POINTER(DwPackDesc), fp, vp], i32),
     'ledn_dw_repack_multi': ([vp, i32, i32, i32, vp], i32),
@@ -298,6 +302,7 @@ _PROTOS = {
     'ledn_aug_crop_hist': ([vp, i32, i32, vp, vp], i32),
     'ledn_dw_unpack_grad': ([C.POINTER(DwPackDesc), fp, vp], i32),
     'ledn_sesp_pyramid': ([C.POINTER(PyrDesc), vp], i32),
+    'ledn_sesp_pyramid_kernel_id': ([C.POINTER(PyrDesc), vp], i32),
     'ledn_channel_stats': ([vp, vp, i64, i32, i32, fp, fp, vp], i32),
     'ledn_bn_finalize': ([fp, fp, C.c_double, fp, fp, fp, fp, C.c_float, C.c_float, fp, fp, fp, fp, i32, vp], i32),
     'ledn_affine_act': ([C.POINTER(AffineDesc), vp], i32),

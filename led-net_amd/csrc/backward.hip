@@ -543,50 +543,89 @@ static int dwbwd_validate(const ledn_dwbwd_desc& d) {
     return LEDN_OK;
 }
 
-int dw3x3_bwd_data_bf16(const ledn_dwbwd_desc& b, hipStream_t s);   // dwconv.hip; -1 = shape not covered
+bool dw3x3_bwd_data_bf16_plan(const ledn_dwbwd_desc& b, DwPlan* p);   // dwconv.hip; false = shape not covered
+int dw3x3_bwd_data_bf16(const ledn_dwbwd_desc& b, const DwPlan& p, hipStream_t s);
 
-int dw8x8_bwd_data_tile(const ledn_dwbwd_desc& b, hipStream_t s);   // dwconv.hip; -1 = shape not covered
+bool dw8x8_bwd_data_tile_applies(const ledn_dwbwd_desc& b, float** scratch_out);   // dwconv.hip
+int dw8x8_bwd_data_tile(const ledn_dwbwd_desc& b, hipStream_t s);                  // -1 = shape not covered
+bool dw8x8_bwd_weight_tile_applies(const ledn_dwbwd_desc& b, long* tiles_out, float** part_out);
 int dw8x8_bwd_weight_tile(const ledn_dwbwd_desc& b, hipStream_t s);
 
-int dw_bwd_data_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
-    int rc = dwbwd_validate(d);
+static int dw_bwd_data_validate(const ledn_dwbwd_desc& d) {
+    const int rc = dwbwd_validate(d);
     if (rc != LEDN_OK) return rc;
     LEDN_REQUIRE(d.w && d.dx);
-    rc = dw8x8_bwd_data_tile(d, s);
-    if (rc >= 0) return rc;
-    if (d.Ho == d.H && d.Wo == d.W) {
-        rc = dw3x3_bwd_data_bf16(d, s);
-        if (rc >= 0) return rc;
+    return LEDN_OK;
+}
+
+// which kernel forms the data gradient of a validated d (order of preference: 8x8 tile, the vectorised 3x3 pair, generic)
+static DwPlan dw_bwd_data_plan(const ledn_dwbwd_desc& d) {
+    DwPlan p;
+    if (dw8x8_bwd_data_tile_applies(d, nullptr)) {
+        p.kid = LEDN_DWBD_TILE8X8;
+        return p;
     }
+    if (d.Ho == d.H && d.Wo == d.W && dw3x3_bwd_data_bf16_plan(d, &p)) return p;
+    if (!dtype_known(d.dtype)) return p;      // kid -1: LEDN_EINVAL
     const bool v4 = d.C % 4 == 0 && d.group_size % 4 == 0;
     const long total = (long)d.N * d.H * d.W * (v4 ? d.C / 4 : d.C);
-    const dim3 grid((unsigned)cdiv(total, 256));
+    p.kid = v4 ? LEDN_DWBD_GENERIC_V4 : LEDN_DWBD_GENERIC_V1;
+    p.nb = cdiv(total, 256);
+    return p;
+}
+
+int dw_bwd_data_kernel_id(const ledn_dwbwd_desc& d) {
+    return dw_bwd_data_validate(d) != LEDN_OK ? -1 : dw_bwd_data_plan(d).kid;
+}
+
+int dw_bwd_data_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
+    const int rc = dw_bwd_data_validate(d);
+    if (rc != LEDN_OK) return rc;
+    const DwPlan p = dw_bwd_data_plan(d);
+    if (p.kid < 0) return LEDN_EINVAL;
+    if (p.kid == LEDN_DWBD_TILE8X8) return dw8x8_bwd_data_tile(d, s);
+    if (p.kid != LEDN_DWBD_GENERIC_V4 && p.kid != LEDN_DWBD_GENERIC_V1) return dw3x3_bwd_data_bf16(d, p, s);
+    const dim3 grid((unsigned)p.nb);
     return with_dtype(d.dtype, [&](auto t) {
         using T = tag_t<decltype(t)>;
-        if (v4) LEDN_LAUNCH((dw_bwd_data_kernel<T, 4>), grid, dim3(256), 0, s, d);
+        if (p.kid == LEDN_DWBD_GENERIC_V4) LEDN_LAUNCH((dw_bwd_data_kernel<T, 4>), grid, dim3(256), 0, s, d);
         else LEDN_LAUNCH((dw_bwd_data_kernel<T, 1>), grid, dim3(256), 0, s, d);
         return check_launch();
     });
 }
 
-int dw3x3_bwd_weight_bf16(const ledn_dwbwd_desc& d, hipStream_t s);   // stencil_bf16.hip; -1 = shape not covered
+bool dw3x3_bwd_weight_bf16_plan(const ledn_dwbwd_desc& d, DwPlan* p);   // stencil_bf16.hip; false = shape not covered
+int dw3x3_bwd_weight_bf16(const ledn_dwbwd_desc& d, const DwPlan& p, hipStream_t s);
+bool pyr_bwd_data_bf16_applies(const ledn_pyrbwd_desc& d);
 int pyr_bwd_data_bf16(const ledn_pyrbwd_desc& d, hipStream_t s);
 bool pyr_tile_applies(const ledn_pyrbwd_desc& d);
 int pyr_bwd_data_tile(const ledn_pyrbwd_desc& d, hipStream_t s);
 bool pyr_ctx_applies(const ledn_pyrbwd_desc& d);
 int pyr_bwd_data_ctx(const ledn_pyrbwd_desc& d, hipStream_t s);
-int pyr_bwd_weight_bf16(const ledn_pyrbwd_desc& d, hipStream_t s);
+bool pyr_bwd_weight_bf16_plan(const ledn_pyrbwd_desc& d, DwPlan* p);
+int pyr_bwd_weight_bf16(const ledn_pyrbwd_desc& d, const DwPlan& p, hipStream_t s);
 
-int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
-    int rc = dwbwd_validate(d);
+static int dw_bwd_weight_validate(const ledn_dwbwd_desc& d) {
+    const int rc = dwbwd_validate(d);
     if (rc != LEDN_OK) return rc;
     LEDN_REQUIRE(d.x && d.dw);
-    rc = dw3x3_bwd_weight_bf16(d, s);
-    if (rc >= 0) return rc;
-    rc = dw8x8_bwd_weight_tile(d, s);
-    if (rc >= 0) return rc;
+    return LEDN_OK;
+}
+
+// which kernel forms the weight gradient of a validated d, on which grid and with which ending (order of preference:
+// vectorised 3x3, 8x8 tile, 3x3 single pass, filter row per workgroup, tap per workgroup)
+static DwPlan dw_bwd_weight_plan(const ledn_dwbwd_desc& d) {
+    DwPlan p;
+    p.reduce = true;
+    if (dw3x3_bwd_weight_bf16_plan(d, &p)) return p;
+    if (dw8x8_bwd_weight_tile_applies(d, &p.rows, &p.part)) {
+        p.kid = LEDN_DWBW_TILE8X8;
+        return p;
+    }
+    p.rows = 0;
+    p.part = nullptr;
     const bool v4 = d.C % 4 == 0 && d.group_size % 4 == 0;
-    LEDN_REQUIRE((v4 ? d.C / 4 : d.C) <= 256);
+    if ((v4 ? d.C / 4 : d.C) > 256 || !dtype_known(d.dtype)) return p;      // kid -1: LEDN_EINVAL
     const long npix = (long)d.N * d.Ho * d.Wo;
     if (d.KH == 3 && d.KW == 3 && v4 && !d.ext1 && 256 % (d.C / 4) == 0) {
         const int rows = 256 / (d.C / 4);
@@ -594,14 +633,10 @@ int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
         if (nb > 1024) nb = 1024;
         float* part = (nb > 32 || det()) ? ws_take(nb * 9 * d.C) : nullptr;
         if (!part && nb > 128) nb = 128;
-        const dim3 g3((unsigned)nb);
-        rc = with_dtype(d.dtype, [&](auto t) {
-            LEDN_LAUNCH((dw_bwd_weight3x3_kernel<tag_t<decltype(t)>, 4>), g3, dim3(256), 0, s, d, part);
-            return LEDN_OK;
-        });
-        if (rc != LEDN_OK) return rc;
-        if (part) return finish_partials(part, (int)nb, 9 * d.C, 1, d.dw, nullptr, nullptr, s);
-        return check_launch();
+        p.kid = LEDN_DWBW_3X3_V4;
+        p.nb = p.rows = nb;
+        p.part = part;
+        return p;
     }
     if (d.KW == 8 && v4 && 256 % (d.C / 4) == 0) {     // GETB 8x8: a filter row per workgroup
         const int rows = 256 / (d.C / 4);
@@ -613,14 +648,11 @@ int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
             ppb = cdiv(cdiv(npix, 64), rows) * rows;
             nbx = cdiv(npix, ppb);
         }
-        const dim3 g8((unsigned)nbx, (unsigned)d.KH);
-        rc = with_dtype(d.dtype, [&](auto t) {
-            LEDN_LAUNCH((dw_bwd_weight_row_kernel<tag_t<decltype(t)>, 4, 8>), g8, dim3(256), 0, s, d, (int)ppb, part);
-            return LEDN_OK;
-        });
-        if (rc != LEDN_OK) return rc;
-        if (part) return finish_partials(part, (int)nbx, d.KH * 8 * d.C, 1, d.dw, nullptr, nullptr, s);
-        return check_launch();
+        p.kid = LEDN_DWBW_ROW_V4_KW8;
+        p.nb = p.rows = nbx;
+        p.ppb = ppb;
+        p.part = part;
+        return p;
     }
     // many short workgroups whose per-tap partial sums go to the workspace (summed by
     // finish_partials), else a bounded grid ending in one atomic per (tap, channel) per workgroup
@@ -634,16 +666,64 @@ int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
         if (ppb < 128) ppb = 128;
         nbx = cdiv(npix, ppb);
     }
-    const dim3 grid((unsigned)nbx, (unsigned)taps);
-    rc = with_dtype(d.dtype, [&](auto t) {
-        using T = tag_t<decltype(t)>;
-        if (v4) LEDN_LAUNCH((dw_bwd_weight_kernel<T, 4>), grid, dim3(256), 0, s, d, (int)ppb, part);
-        else LEDN_LAUNCH((dw_bwd_weight_kernel<T, 1>), grid, dim3(256), 0, s, d, (int)ppb, part);
-        return LEDN_OK;
-    });
+    p.kid = v4 ? LEDN_DWBW_TAP_V4 : LEDN_DWBW_TAP_V1;
+    p.nb = p.rows = nbx;
+    p.ppb = ppb;
+    p.part = part;
+    return p;
+}
+
+int dw_bwd_weight_kernel_id(const ledn_dwbwd_desc& d) {
+    if (dw_bwd_weight_validate(d) != LEDN_OK) return -1;
+    const DwPlan p = dw_bwd_weight_plan(d);
+    return p.kid < 0 ? -1 : p.kid | p.ending();
+}
+
+int dw_bwd_weight_impl(const ledn_dwbwd_desc& d, hipStream_t s) {
+    int rc = dw_bwd_weight_validate(d);
     if (rc != LEDN_OK) return rc;
-    if (part) return finish_partials(part, (int)nbx, taps * d.C, 1, d.dw, nullptr, nullptr, s);
-    return check_launch();
+    const DwPlan p = dw_bwd_weight_plan(d);
+    float* part = p.part;
+    const int ppb = (int)p.ppb;
+    switch (p.kid) {
+    case LEDN_DWBW_BF16_3X3: return dw3x3_bwd_weight_bf16(d, p, s);
+    case LEDN_DWBW_TILE8X8: return dw8x8_bwd_weight_tile(d, s);
+    case LEDN_DWBW_3X3_V4: {
+        const dim3 g3((unsigned)p.nb);
+        rc = with_dtype(d.dtype, [&](auto t) {
+            LEDN_LAUNCH((dw_bwd_weight3x3_kernel<tag_t<decltype(t)>, 4>), g3, dim3(256), 0, s, d, part);
+            return LEDN_OK;
+        });
+        if (rc != LEDN_OK) return rc;
+        if (part) return finish_partials(part, (int)p.rows, 9 * d.C, 1, d.dw, nullptr, nullptr, s);
+        return check_launch();
+    }
+    case LEDN_DWBW_ROW_V4_KW8: {
+        const dim3 g8((unsigned)p.nb, (unsigned)d.KH);
+        rc = with_dtype(d.dtype, [&](auto t) {
+            LEDN_LAUNCH((dw_bwd_weight_row_kernel<tag_t<decltype(t)>, 4, 8>), g8, dim3(256), 0, s, d, ppb, part);
+            return LEDN_OK;
+        });
+        if (rc != LEDN_OK) return rc;
+        if (part) return finish_partials(part, (int)p.rows, d.KH * 8 * d.C, 1, d.dw, nullptr, nullptr, s);
+        return check_launch();
+    }
+    case LEDN_DWBW_TAP_V4:
+    case LEDN_DWBW_TAP_V1: {
+        const int taps = d.KH * d.KW;
+        const dim3 grid((unsigned)p.nb, (unsigned)taps);
+        rc = with_dtype(d.dtype, [&](auto t) {
+            using T = tag_t<decltype(t)>;
+            if (p.kid == LEDN_DWBW_TAP_V4) LEDN_LAUNCH((dw_bwd_weight_kernel<T, 4>), grid, dim3(256), 0, s, d, ppb, part);
+            else LEDN_LAUNCH((dw_bwd_weight_kernel<T, 1>), grid, dim3(256), 0, s, d, ppb, part);
+            return LEDN_OK;
+        });
+        if (rc != LEDN_OK) return rc;
+        if (part) return finish_partials(part, (int)p.rows, taps * d.C, 1, d.dw, nullptr, nullptr, s);
+        return check_launch();
+    }
+    default: return LEDN_EINVAL;
+    }
 }
 
 int dw3x3_bwd_fused(const ledn_dwbwd_desc& b, hipStream_t s);   // dwconv.hip; -1 = shape not covered
@@ -812,37 +892,58 @@ int pyr_bwd_data_kernel_id(const ledn_pyrbwd_desc& d) {
     if (pyrbwd_validate(d) != LEDN_OK) return -1;
     if (pyr_tile_applies(d)) return 2;
     if (pyr_ctx_applies(d)) return 3;
-    const int cvn = d.n / 8;
-    return d.dtype == LEDN_BF16 && d.stride == 1 && d.n % 8 == 0 && 256 % cvn == 0 && cvn <= 256 &&
-                   (long)d.N * d.H * d.W * d.n * 4 < (1L << 31)
-               ? 1
-               : 0;
+    return pyr_bwd_data_bf16_applies(d) ? 1 : 0;      // (the gate implies n % 4 == 0, which pyr_bwd_data_impl asks first)
 }
 
-int pyr_bwd_weight_impl(const ledn_pyrbwd_desc& d, hipStream_t s) {
-    int rc = pyrbwd_validate(d);
+static int pyr_bwd_weight_validate(const ledn_pyrbwd_desc& d) {
+    const int rc = pyrbwd_validate(d);
     if (rc != LEDN_OK) return rc;
     LEDN_REQUIRE(d.x && d.dw);
-    rc = pyr_bwd_weight_bf16(d, s);
-    if (rc >= 0) return rc;
+    return LEDN_OK;
+}
+
+// which kernel forms the pyramid's weight gradient of a validated d, on which grid and with which ending
+static DwPlan pyr_bwd_weight_plan(const ledn_pyrbwd_desc& d) {
+    DwPlan p;
+    p.reduce = true;
+    if (pyr_bwd_weight_bf16_plan(d, &p)) return p;
     const bool v4 = d.n % 4 == 0;
-    LEDN_REQUIRE((v4 ? d.n / 4 : d.n) <= 256);
-    const long npix = (long)d.N * d.Ho * d.Wo;
     const int cvn = v4 ? d.n / 4 : d.n;
+    if (cvn > 256) return p;      // kid -1: LEDN_EINVAL (the dtype is F32 or BF16: pyrbwd_validate)
+    const long npix = (long)d.N * d.Ho * d.Wo;
     const int rows = 256 / cvn;
     long nb = cdiv(npix, rows * 8);
     if (nb > 512) nb = 512;
     float* part = (nb > 32 || det()) ? ws_take(nb * 36 * d.n) : nullptr;
     if (!part && nb > 128) nb = 128;
-    const dim3 grid((unsigned)nb, 4u);
+    p.kid = v4 ? LEDN_PYRBW_GENERIC_V4 : LEDN_PYRBW_GENERIC_V1;
+    p.nb = p.rows = nb;
+    p.part = part;
+    return p;
+}
+
+int pyr_bwd_weight_kernel_id(const ledn_pyrbwd_desc& d) {
+    if (pyr_bwd_weight_validate(d) != LEDN_OK) return -1;
+    const DwPlan p = pyr_bwd_weight_plan(d);
+    return p.kid < 0 ? -1 : p.kid | p.ending();
+}
+
+int pyr_bwd_weight_impl(const ledn_pyrbwd_desc& d, hipStream_t s) {
+    int rc = pyr_bwd_weight_validate(d);
+    if (rc != LEDN_OK) return rc;
+    const DwPlan p = pyr_bwd_weight_plan(d);
+    if (p.kid < 0) return LEDN_EINVAL;
+    if (p.kid != LEDN_PYRBW_GENERIC_V4 && p.kid != LEDN_PYRBW_GENERIC_V1) return pyr_bwd_weight_bf16(d, p, s);
+    float* part = p.part;
+    const dim3 grid((unsigned)p.nb, 4u);
     rc = with_dtype(d.dtype, [&](auto t) {
         using T = tag_t<decltype(t)>;
-        if (v4) LEDN_LAUNCH((pyr_bwd_weight_kernel<T, 4>), grid, dim3(256), 0, s, d, part);
+        if (p.kid == LEDN_PYRBW_GENERIC_V4) LEDN_LAUNCH((pyr_bwd_weight_kernel<T, 4>), grid, dim3(256), 0, s, d, part);
         else LEDN_LAUNCH((pyr_bwd_weight_kernel<T, 1>), grid, dim3(256), 0, s, d, part);
         return LEDN_OK;
     });
     if (rc != LEDN_OK) return rc;
-    if (part) return finish_partials(part, (int)nb, 36 * d.n, 1, d.dw, nullptr, nullptr, s);
+    if (part) return finish_partials(part, (int)p.rows, 36 * d.n, 1, d.dw, nullptr, nullptr, s);
     return check_launch();
 }
 

@@ -34,6 +34,8 @@ int pack_conv_weights_impl(const float* w, void* out, int Cout, int Cin, int KH,
 int wgrad_validate(const ledn_wgrad_desc& d);
 int conv_wgrad_direct(const ledn_wgrad_desc& d, hipStream_t s);
 int dwconv_impl(const ledn_dw_desc& d, hipStream_t s);
+int dwconv_kernel_id(const ledn_dw_desc& d);
+int sesp_pyramid_kernel_id(const ledn_pyr_desc& d);
 int iou_hist_impl(const unsigned char* pred, const long long* label, long long P, int num_classes,
                   int ignore_index, float* hist, hipStream_t s);
 int bn_finalize_rows_impl(const float* part, int rows, double count, const float* gamma, const float* beta,
@@ -97,6 +99,9 @@ bool dw3x3_bwd_fused_applies(const ledn_dwbwd_desc& b);
 int pyr_bwd_data_impl(const ledn_pyrbwd_desc& d, hipStream_t s);
 int pyr_bwd_weight_impl(const ledn_pyrbwd_desc& d, hipStream_t s);
 int pyr_bwd_data_kernel_id(const ledn_pyrbwd_desc& d);
+int dw_bwd_data_kernel_id(const ledn_dwbwd_desc& d);
+int dw_bwd_weight_kernel_id(const ledn_dwbwd_desc& d);
+int pyr_bwd_weight_kernel_id(const ledn_pyrbwd_desc& d);
 int bilinear_bwd_impl(const void* dy, void* dx, int N, int H, int W, int C, int Ho, int Wo, int dtype_dy,
                       int dtype_dx, hipStream_t s);
 int avgpool3x3s2_bwd_impl(const void* dy, const void* add, void* dx, int N, int H, int W, int C, int Ho,
@@ -383,6 +388,8 @@ int ledn_iou_hist(const unsigned char* pred, const long long* label, long long P
     return iou_hist_impl(pred, label, P, num_classes, ignore_index, hist, S(stream));
 }
 int ledn_dwconv2d(const ledn_dw_desc* d, void* stream) { return d ? dwconv_impl(*d, S(stream)) : LEDN_EINVAL; }
+// the kernel-id queries enter the stream like their entries do: the plan reads the workspace bound to it
+int ledn_dwconv2d_kernel_id(const ledn_dw_desc* d, void* stream) { return d ? (S(stream), dwconv_kernel_id(*d)) : -1; }
 int ledn_dw_pack(const ledn_dwpack_desc* d, float* packed, void* stream) {
     return d ? dw_pack_impl(*d, packed, S(stream)) : LEDN_EINVAL;
 }
@@ -392,6 +399,7 @@ int ledn_dw_unpack_grad(const ledn_dwpack_desc* d, const float* dpacked, void* s
 int ledn_sesp_pyramid(const ledn_pyr_desc* d, void* stream) {
     return d ? sesp_pyramid_impl(*d, S(stream)) : LEDN_EINVAL;
 }
+int ledn_sesp_pyramid_kernel_id(const ledn_pyr_desc* d, void* stream) { return d ? (S(stream), sesp_pyramid_kernel_id(*d)) : -1; }
 
 int ledn_channel_stats(const void* x, const void* xadd, long long P, int C, int dtype, float* sum,
                        float* sqsum, void* stream) {
@@ -522,6 +530,12 @@ int ledn_dwconv2d_bwd_data(const ledn_dwbwd_desc* d, void* stream) {
 int ledn_dwconv2d_bwd_weight(const ledn_dwbwd_desc* d, void* stream) {
     return d ? dw_bwd_weight_impl(*d, S(stream)) : LEDN_EINVAL;
 }
+int ledn_dwconv2d_bwd_data_kernel_id(const ledn_dwbwd_desc* d, void* stream) {
+    return d ? (S(stream), dw_bwd_data_kernel_id(*d)) : -1;
+}
+int ledn_dwconv2d_bwd_weight_kernel_id(const ledn_dwbwd_desc* d, void* stream) {
+    return d ? (S(stream), dw_bwd_weight_kernel_id(*d)) : -1;
+}
 int ledn_dwconv2d_bwd(const ledn_dwbwd_desc* d, void* stream) { return d ? dw_bwd_impl(*d, S(stream)) : LEDN_EINVAL; }
 int ledn_dwconv2d_bwd_fused_applies(const ledn_dwbwd_desc* d) { return d && dw3x3_bwd_fused_applies(*d) ? 1 : 0; }
 int ledn_sesp_pyramid_bwd_data(const ledn_pyrbwd_desc* d, void* stream) {
@@ -531,6 +545,9 @@ int ledn_sesp_pyramid_bwd_weight(const ledn_pyrbwd_desc* d, void* stream) {
     return d ? pyr_bwd_weight_impl(*d, S(stream)) : LEDN_EINVAL;
 }
 int ledn_sesp_pyramid_bwd_kernel_id(const ledn_pyrbwd_desc* d) { return d ? pyr_bwd_data_kernel_id(*d) : -1; }
+int ledn_sesp_pyramid_bwd_weight_kernel_id(const ledn_pyrbwd_desc* d, void* stream) {
+    return d ? (S(stream), pyr_bwd_weight_kernel_id(*d)) : -1;
+}
 int ledn_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, int C, int Ho, int Wo, int dtype_dy,
                       int dtype_dx, void* stream) {
     return bilinear_bwd_impl(dy, dx, N, H, W, C, Ho, Wo, dtype_dy, dtype_dx, S(stream));

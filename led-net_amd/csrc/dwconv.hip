@@ -551,17 +551,31 @@ __global__ void __launch_bounds__(256) dw8x8_fold_kernel(const bf16_t* t, const 
     st8(dx + pix * C + c, acc);
 }
 
-int dw8x8_bwd_data_tile(const ledn_dwbwd_desc& b, hipStream_t s) {   // used by backward.hip; -1 = shape not covered
+// shape class of the two tiled 8x8 gradients (data: dw8x8_tile_kernel<1> + fold, weight: dw8x8_wgrad_tile_kernel)
+static bool dw8x8_bwd_shape_ok(const ledn_dwbwd_desc& b) {
     if (!(options().stream_fast & 2) || b.dtype != LEDN_BF16 || b.KH != 8 || b.KW != 8 || b.stride != 1 || b.pad != 3 ||
         !b.ext1 || b.C % 32 || b.Ho != b.H || b.Wo != b.W || b.H < 2 || b.W < 2)
-        return -1;
+        return false;
     for (int g = 0; g * b.group_size < b.C; ++g)
-        if (b.dil[g] != 1) return -1;
+        if (b.dil[g] != 1) return false;
+    return true;
+}
+
+// the tiled 8x8 data gradient takes b (needs the workspace for the gradient of the extended map); *scratch_out = that buffer
+bool dw8x8_bwd_data_tile_applies(const ledn_dwbwd_desc& b, float** scratch_out) {   // used by backward.hip
+    if (!dw8x8_bwd_shape_ok(b)) return false;
     const long npix = (long)b.N * b.H * b.W;
     const long ext = (long)b.N * (b.H + 1) * (b.W + 1) * b.C;
-    if (npix < 4096 || ext >= (1L << 31)) return -1;
+    if (npix < 4096 || ext >= (1L << 31)) return false;
     float* scratch = ws_take(cdiv(ext, 2));
-    if (!scratch) return -1;
+    if (scratch_out) *scratch_out = scratch;
+    return scratch != nullptr;
+}
+
+int dw8x8_bwd_data_tile(const ledn_dwbwd_desc& b, hipStream_t s) {   // used by backward.hip; -1 = shape not covered
+    float* scratch = nullptr;
+    if (!dw8x8_bwd_data_tile_applies(b, &scratch)) return -1;
+    const long npix = (long)b.N * b.H * b.W;
     ledn_dw_desc d = {};
     d.x = b.dz; d.w = b.w; d.y = scratch;
     d.N = b.N; d.H = b.H; d.W = b.W; d.C = b.C; d.Ho = b.H + 1; d.Wo = b.W + 1;
@@ -667,54 +681,70 @@ __global__ void __launch_bounds__(256) dw8x8_wgrad_tile_kernel(ledn_dwbwd_desc d
     }
 }
 
-int dw8x8_bwd_weight_tile(const ledn_dwbwd_desc& b, hipStream_t s) {   // used by backward.hip; -1 = shape not covered
-    if (!(options().stream_fast & 2) || b.dtype != LEDN_BF16 || b.KH != 8 || b.KW != 8 || b.stride != 1 || b.pad != 3 ||
-        !b.ext1 || b.C % 32 || b.Ho != b.H || b.Wo != b.W || b.H < 2 || b.W < 2)
-        return -1;
-    for (int g = 0; g * b.group_size < b.C; ++g)
-        if (b.dil[g] != 1) return -1;
+// the tiled 8x8 weight gradient takes b (one partial row per tile: needs the workspace); fills the plan's grid and rows
+bool dw8x8_bwd_weight_tile_applies(const ledn_dwbwd_desc& b, long* tiles_out, float** part_out) {   // used by backward.hip
+    if (!dw8x8_bwd_shape_ok(b)) return false;
     const long npix = (long)b.N * b.H * b.W;
-    if (npix < 4096 || npix * b.C >= (1L << 31)) return -1;
+    if (npix < 4096 || npix * b.C >= (1L << 31)) return false;
     const long tiles = (long)b.N * cdiv(b.Ho, 8) * cdiv(b.Wo, 32);
     float* part = ws_take(tiles * 64 * b.C);
-    if (!part) return -1;
+    if (tiles_out) *tiles_out = tiles;
+    if (part_out) *part_out = part;
+    return part != nullptr;
+}
+
+int dw8x8_bwd_weight_tile(const ledn_dwbwd_desc& b, hipStream_t s) {   // used by backward.hip; -1 = shape not covered
+    long tiles = 0;
+    float* part = nullptr;
+    if (!dw8x8_bwd_weight_tile_applies(b, &tiles, &part)) return -1;
     LEDN_LAUNCH(dw8x8_wgrad_tile_kernel, dim3((unsigned)(tiles * (b.C / 32))), dim3(256), 0, s, b, part);
     return finish_partials(part, (int)tiles, 64 * b.C, 1, b.dw, nullptr, nullptr, s);
 }
 
-// launches the tiled kernel when it applies (returns the number of partial rows through *rows), else -1
-static int dw3x3_tile_launch(const ledn_dw_desc& d, bool flip, const bf16_t* add, bool want_stats, float** part_out,
-                             long* rows_out, hipStream_t s) {
-    if (d.C % 32 || d.group_size % 8 || d.W < 32 || (long)d.N * d.H * d.W < 16384) return -1;
+// the tiled 3x3 kernel applies (forward: flip = false; data gradient: flip = true); p->kid is set to the instance
+static bool dw3x3_tile_plan(const ledn_dw_desc& d, bool flip, bool want_stats, DwPlan* p) {
+    if (d.C % 32 || d.group_size % 8 || d.W < 32 || (long)d.N * d.H * d.W < 16384) return false;
     int hl = 0;
     for (int g = 0; g * d.group_size < d.C; ++g) hl = d.dil[g] > hl ? d.dil[g] : hl;
-    if (hl > 5) return -1;
+    if (hl > 5) return false;
     static const int th2 = (int)exp_knob("LEDN_DW_TH", 16);      // (A/B knob: 8 = more, shorter workgroups for dilation <= 2)
     const int TH = (hl <= 2 && th2 != 8) ? 16 : 8;
     const long tiles = (long)d.N * cdiv(d.H, TH) * cdiv(d.W, 32);
     const long nb = tiles * (d.C / 32);
-    if (nb > (1L << 30) || tiles > 16384) return -1;
+    if (nb > (1L << 30) || tiles > 16384) return false;
     float* part = nullptr;
     if (want_stats) {
         part = ws_take(tiles * 2 * d.C);
-        if (!part) return -1;
+        if (!part) return false;
     }
     const bool plain = !flip && !d.out_scale && !d.out_shift && d.act_out == LEDN_ACT_NONE;     // the training forward
-    if (hl <= 2 && TH == 16) {
-        if (flip) LEDN_LAUNCH((dw3x3_tile_kernel<1, 2, 16>), dim3((unsigned)nb), dim3(256), 0, s, d, add, part);
-        else if (plain) LEDN_LAUNCH((dw3x3_tile_kernel<0, 2, 16, false>), dim3((unsigned)nb), dim3(256), 0, s, d, add, part);
-        else LEDN_LAUNCH((dw3x3_tile_kernel<0, 2, 16>), dim3((unsigned)nb), dim3(256), 0, s, d, add, part);
-    } else if (hl <= 2) {
-        if (flip) LEDN_LAUNCH((dw3x3_tile_kernel<1, 2, 8>), dim3((unsigned)nb), dim3(256), 0, s, d, add, part);
-        else LEDN_LAUNCH((dw3x3_tile_kernel<0, 2, 8>), dim3((unsigned)nb), dim3(256), 0, s, d, add, part);
-    } else {
-        if (flip) LEDN_LAUNCH((dw3x3_tile_kernel<1, 5, 8>), dim3((unsigned)nb), dim3(256), 0, s, d, add, part);
-        else if (plain) LEDN_LAUNCH((dw3x3_tile_kernel<0, 5, 8, false>), dim3((unsigned)nb), dim3(256), 0, s, d, add, part);
-        else LEDN_LAUNCH((dw3x3_tile_kernel<0, 5, 8>), dim3((unsigned)nb), dim3(256), 0, s, d, add, part);
+    if (hl <= 2 && TH == 16) p->kid = flip ? LEDN_DWBD_TILE_2_16 : plain ? LEDN_DW_TILE_2_16_PLAIN : LEDN_DW_TILE_2_16;
+    else if (hl <= 2) p->kid = flip ? LEDN_DWBD_TILE_2_8 : LEDN_DW_TILE_2_8;
+    else p->kid = flip ? LEDN_DWBD_TILE_5_8 : plain ? LEDN_DW_TILE_5_8_PLAIN : LEDN_DW_TILE_5_8;
+    p->nb = nb;
+    p->rows = tiles;
+    p->part = part;
+    p->reduce = want_stats;
+    return true;
+}
+
+// launches the tiled kernel a dw3x3_tile_plan chose
+static void dw3x3_tile_launch(const ledn_dw_desc& d, bool flip, const DwPlan& p, const bf16_t* add, hipStream_t s) {
+    const dim3 grid((unsigned)p.nb);
+    float* part = p.part;
+    if (flip) {
+        if (p.kid == LEDN_DWBD_TILE_2_16) LEDN_LAUNCH((dw3x3_tile_kernel<1, 2, 16>), grid, dim3(256), 0, s, d, add, part);
+        else if (p.kid == LEDN_DWBD_TILE_2_8) LEDN_LAUNCH((dw3x3_tile_kernel<1, 2, 8>), grid, dim3(256), 0, s, d, add, part);
+        else LEDN_LAUNCH((dw3x3_tile_kernel<1, 5, 8>), grid, dim3(256), 0, s, d, add, part);
+        return;
     }
-    *part_out = part;
-    *rows_out = tiles;
-    return 0;
+    switch (p.kid) {
+    case LEDN_DW_TILE_2_16_PLAIN: LEDN_LAUNCH((dw3x3_tile_kernel<0, 2, 16, false>), grid, dim3(256), 0, s, d, add, part); break;
+    case LEDN_DW_TILE_2_16: LEDN_LAUNCH((dw3x3_tile_kernel<0, 2, 16>), grid, dim3(256), 0, s, d, add, part); break;
+    case LEDN_DW_TILE_2_8: LEDN_LAUNCH((dw3x3_tile_kernel<0, 2, 8>), grid, dim3(256), 0, s, d, add, part); break;
+    case LEDN_DW_TILE_5_8_PLAIN: LEDN_LAUNCH((dw3x3_tile_kernel<0, 5, 8, false>), grid, dim3(256), 0, s, d, add, part); break;
+    default: LEDN_LAUNCH((dw3x3_tile_kernel<0, 5, 8>), grid, dim3(256), 0, s, d, add, part); break;
+    }
 }
 
 // shape gate of the vectorised 3x3 kernels (forward and data gradient)
@@ -727,24 +757,35 @@ static bool dw3x3_bf16_ok(int C, int group_size, int KH, int KW, int stride, int
     return true;
 }
 
-int dw3x3_bwd_data_bf16(const ledn_dwbwd_desc& b, hipStream_t s) {   // used by backward.hip
-    if (b.dtype != LEDN_BF16 || !dw3x3_bf16_ok(b.C, b.group_size, b.KH, b.KW, b.stride, b.pad, b.ext1, b.dil,
-                                               (long)b.N * b.H * b.W * b.C))
-        return -1;
+// the forward descriptor whose flipped-tap run is b's data gradient (x = dz, y = dx)
+static ledn_dw_desc dw3x3_flip_desc(const ledn_dwbwd_desc& b) {
     ledn_dw_desc d = {};
     d.x = b.dz; d.w = b.w; d.y = b.dx;
     d.N = b.N; d.H = b.H; d.W = b.W; d.C = b.C; d.Ho = b.H; d.Wo = b.W;
     d.KH = d.KW = 3; d.stride = 1; d.pad = b.pad; d.group_size = b.group_size;
     for (int i = 0; i < 4; ++i) d.dil[i] = b.dil[i];
-    if (options().stream_fast & 2) {
-        float* part = nullptr;
-        long rows = 0;
-        if (dw3x3_tile_launch(d, true, (const bf16_t*)b.add, false, &part, &rows, s) == 0) return check_launch();
-    }
+    return d;
+}
+
+// the vectorised 3x3 data gradients take b (the caller has checked Ho == H, Wo == W): LEDN_DWBD_TILE_* or LEDN_DWBD_BF16
+bool dw3x3_bwd_data_bf16_plan(const ledn_dwbwd_desc& b, DwPlan* p) {   // used by backward.hip
+    if (b.dtype != LEDN_BF16 || !dw3x3_bf16_ok(b.C, b.group_size, b.KH, b.KW, b.stride, b.pad, b.ext1, b.dil,
+                                               (long)b.N * b.H * b.W * b.C))
+        return false;
+    const ledn_dw_desc d = dw3x3_flip_desc(b);
+    if ((options().stream_fast & 2) && dw3x3_tile_plan(d, true, false, p)) return true;
     const int rows = 256 / (d.C / 8);
     long nb = cdiv((long)d.N * d.H * d.W, rows * 4);
     if (nb > 2048) nb = 2048;
-    LEDN_LAUNCH((dw3x3_bf16_kernel<1>), dim3((unsigned)nb), dim3(256), 0, s, d, (const bf16_t*)b.add, (float*)nullptr);
+    p->kid = LEDN_DWBD_BF16;
+    p->nb = nb;
+    return true;
+}
+
+int dw3x3_bwd_data_bf16(const ledn_dwbwd_desc& b, const DwPlan& p, hipStream_t s) {   // used by backward.hip
+    const ledn_dw_desc d = dw3x3_flip_desc(b);
+    if (p.kid != LEDN_DWBD_BF16) dw3x3_tile_launch(d, true, p, (const bf16_t*)b.add, s);
+    else LEDN_LAUNCH((dw3x3_bf16_kernel<1>), dim3((unsigned)p.nb), dim3(256), 0, s, d, (const bf16_t*)b.add, (float*)nullptr);
     return check_launch();
 }
 
@@ -916,7 +957,7 @@ int dw3x3_bwd_fused(const ledn_dwbwd_desc& b, hipStream_t s) {   // used by back
     return finish_partials(part, (int)R, 9 * b.C, 1, b.dw, nullptr, nullptr, s);
 }
 
-int dwconv_impl(const ledn_dw_desc& d, hipStream_t s) {
+static int dwconv_validate(const ledn_dw_desc& d) {
     LEDN_REQUIRE(d.x && d.w && d.y);
     LEDN_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.C > 0 && d.Ho > 0 && d.Wo > 0);
     LEDN_REQUIRE(d.KH > 0 && d.KW > 0 && d.stride > 0 && d.group_size > 0);
@@ -932,27 +973,30 @@ int dwconv_impl(const ledn_dw_desc& d, hipStream_t s) {
         LEDN_REQUIRE(d.Ho == (Hx + 2 * ph - ((d.KH - 1) * d.dil[g] + 1)) / d.stride + 1);
         LEDN_REQUIRE(d.Wo == (Wx + 2 * pw - ((d.KW - 1) * d.dil[g] + 1)) / d.stride + 1);
     }
+    return LEDN_OK;
+}
+
+// which kernel runs a validated d, on which grid and with which ending of the statistics (the order of the gates is the
+// order of preference: 8x8 tile, 3x3 tile, vectorised 3x3, generic)
+static DwPlan dwconv_plan(const ledn_dw_desc& d) {
+    DwPlan p;
+    p.reduce = d.stat_sum != nullptr;
     if (dw8x8_tile_ok(d)) {
         const long tiles = (long)d.N * cdiv(d.Ho, 8) * cdiv(d.Wo, 32);
         float* part = nullptr;
         if (d.stat_sum) part = ws_take(tiles * 2 * d.C);
         if (!d.stat_sum || part) {
-            LEDN_LAUNCH((dw8x8_tile_kernel<0>), dim3((unsigned)(tiles * (d.C / 32))), dim3(256), 0, s, d, part, 3);
-            if (part) return finish_partials(part, (int)tiles, d.C, 2, d.stat_sum, d.stat_sqsum, nullptr, s);
-            return check_launch();
+            p.kid = LEDN_DW_TILE8X8;
+            p.nb = tiles * (d.C / 32);
+            p.rows = tiles;
+            p.part = part;
+            return p;
         }
     }
     if (d.dtype_x == LEDN_BF16 && d.dtype_y == LEDN_BF16 && d.act_out != LEDN_ACT_SIGMOID && d.Ho == d.H &&
         d.Wo == d.W &&
         dw3x3_bf16_ok(d.C, d.group_size, d.KH, d.KW, d.stride, d.pad, d.ext1, d.dil, (long)d.N * d.H * d.W * d.C)) {
-        if (options().stream_fast & 2) {
-            float* partt = nullptr;
-            long rowst = 0;
-            if (dw3x3_tile_launch(d, false, nullptr, d.stat_sum != nullptr, &partt, &rowst, s) == 0) {
-                if (partt) return finish_partials(partt, (int)rowst, d.C, 2, d.stat_sum, d.stat_sqsum, nullptr, s);
-                return check_launch();
-            }
-        }
+        if ((options().stream_fast & 2) && dw3x3_tile_plan(d, false, d.stat_sum != nullptr, &p)) return p;
         const int rows8 = 256 / (d.C / 8);
         long nb8 = cdiv((long)d.N * d.H * d.W, rows8 * 4);
         if (nb8 > 2048) nb8 = 2048;
@@ -961,13 +1005,14 @@ int dwconv_impl(const ledn_dw_desc& d, hipStream_t s) {
             if (nb8 > 64 || det()) part8 = ws_take(nb8 * 2 * d.C);
             if (!part8 && nb8 > 256) nb8 = 256;
         }
-        LEDN_LAUNCH((dw3x3_bf16_kernel<0>), dim3((unsigned)nb8), dim3(256), 0, s, d, (const bf16_t*)nullptr, part8);
-        if (part8) return finish_partials(part8, (int)nb8, d.C, 2, d.stat_sum, d.stat_sqsum, nullptr, s);
-        return check_launch();
+        p.kid = LEDN_DW_BF16;
+        p.nb = p.rows = nb8;
+        p.part = part8;
+        return p;
     }
     const bool v4 = d.C % 4 == 0 && d.group_size % 4 == 0;
     const int cvn = v4 ? d.C / 4 : d.C;
-    LEDN_REQUIRE(cvn <= 256);
+    if (cvn > 256 || !dtype_known(d.dtype_x) || !dtype_known(d.dtype_y)) return p;      // kid -1: LEDN_EINVAL
     const int rows = 256 / cvn;
     const long npix = (long)d.N * d.Ho * d.Wo;
     long nb = cdiv(npix, rows * 4);
@@ -977,18 +1022,44 @@ int dwconv_impl(const ledn_dw_desc& d, hipStream_t s) {
         if (nb > 64 || det()) part = ws_take(nb * 2 * d.C);
         if (!part && nb > 256) nb = 256;
     }
-    const dim3 grid((unsigned)nb);
-    const bool k3 = d.KH == 3 && d.KW == 3;
-    const int rc = with_dtypes(d.dtype_x, d.dtype_y, [&](auto tx, auto ty) {
-        using TX = tag_t<decltype(tx)>;
-        using TY = tag_t<decltype(ty)>;
-        if (v4 && k3) LEDN_LAUNCH((dwconv_kernel<TX, TY, 4, 9>), grid, dim3(256), 0, s, d, part);
-        else if (v4) LEDN_LAUNCH((dwconv_kernel<TX, TY, 4, 0>), grid, dim3(256), 0, s, d, part);
-        else LEDN_LAUNCH((dwconv_kernel<TX, TY, 1, 0>), grid, dim3(256), 0, s, d, part);
-        return LEDN_OK;
-    });
+    p.kid = !v4 ? LEDN_DW_GENERIC_V1 : (d.KH == 3 && d.KW == 3) ? LEDN_DW_GENERIC_V4_3X3 : LEDN_DW_GENERIC_V4;
+    p.nb = p.rows = nb;
+    p.part = part;
+    return p;
+}
+
+int dwconv_kernel_id(const ledn_dw_desc& d) {
+    if (dwconv_validate(d) != LEDN_OK) return -1;
+    const DwPlan p = dwconv_plan(d);
+    return p.kid < 0 ? -1 : p.kid | p.ending();
+}
+
+int dwconv_impl(const ledn_dw_desc& d, hipStream_t s) {
+    int rc = dwconv_validate(d);
     if (rc != LEDN_OK) return rc;
-    if (part) return finish_partials(part, (int)nb, d.C, 2, d.stat_sum, d.stat_sqsum, nullptr, s);
+    const DwPlan p = dwconv_plan(d);
+    const dim3 grid((unsigned)p.nb);
+    float* part = p.part;
+    switch (p.kid) {
+    case LEDN_DW_TILE8X8: LEDN_LAUNCH((dw8x8_tile_kernel<0>), grid, dim3(256), 0, s, d, part, 3); break;
+    case LEDN_DW_BF16: LEDN_LAUNCH((dw3x3_bf16_kernel<0>), grid, dim3(256), 0, s, d, (const bf16_t*)nullptr, part); break;
+    case LEDN_DW_GENERIC_V1:
+    case LEDN_DW_GENERIC_V4:
+    case LEDN_DW_GENERIC_V4_3X3:
+        rc = with_dtypes(d.dtype_x, d.dtype_y, [&](auto tx, auto ty) {
+            using TX = tag_t<decltype(tx)>;
+            using TY = tag_t<decltype(ty)>;
+            if (p.kid == LEDN_DW_GENERIC_V4_3X3) LEDN_LAUNCH((dwconv_kernel<TX, TY, 4, 9>), grid, dim3(256), 0, s, d, part);
+            else if (p.kid == LEDN_DW_GENERIC_V4) LEDN_LAUNCH((dwconv_kernel<TX, TY, 4, 0>), grid, dim3(256), 0, s, d, part);
+            else LEDN_LAUNCH((dwconv_kernel<TX, TY, 1, 0>), grid, dim3(256), 0, s, d, part);
+            return LEDN_OK;
+        });
+        if (rc != LEDN_OK) return rc;
+        break;
+    case -1: return LEDN_EINVAL;
+    default: dw3x3_tile_launch(d, false, p, nullptr, s); break;
+    }
+    if (part) return finish_partials(part, (int)p.rows, d.C, 2, d.stat_sum, d.stat_sqsum, nullptr, s);
     return check_launch();
 }
 
@@ -1026,24 +1097,42 @@ __global__ void __launch_bounds__(256) sesp_pyramid_kernel(ledn_pyr_desc d) {
     }
 }
 
-int pyr_fwd_bf16(const ledn_pyr_desc& d, hipStream_t s);   // stencil_bf16.hip; -1 = shape not covered
+bool pyr_fwd_bf16_plan(const ledn_pyr_desc& d, DwPlan* p);   // stencil_bf16.hip; false = shape not covered
+int pyr_fwd_bf16(const ledn_pyr_desc& d, const DwPlan& p, hipStream_t s);
 
-int sesp_pyramid_impl(const ledn_pyr_desc& d, hipStream_t s) {
+static int sesp_pyramid_validate(const ledn_pyr_desc& d) {
     LEDN_REQUIRE(d.x && d.w && d.y);
     LEDN_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.n > 0 && (d.stride == 1 || d.stride == 2));
     LEDN_REQUIRE(d.Ho == (d.H - 1) / d.stride + 1 && d.Wo == (d.W - 1) / d.stride + 1);
     for (int b = 0; b < 4; ++b) LEDN_REQUIRE(d.dil[b] > 0);
-    {
-        const int rc = pyr_fwd_bf16(d, s);
-        if (rc >= 0) return rc;
-    }
+    return LEDN_OK;
+}
+
+static DwPlan sesp_pyramid_plan(const ledn_pyr_desc& d) {
+    DwPlan p;
+    if (pyr_fwd_bf16_plan(d, &p)) return p;
+    if (d.dtype_y != d.dtype_x || !dtype_known(d.dtype_x)) return p;   // no mixed-dtype pyramid kernel (kid -1: LEDN_EINVAL)
     const bool v4 = d.n % 4 == 0;
     const long total = (long)d.N * d.Ho * d.Wo * (v4 ? d.n / 4 : d.n);
-    const dim3 grid((unsigned)cdiv(total, 256));
-    LEDN_REQUIRE(d.dtype_y == d.dtype_x);   // no mixed-dtype pyramid kernel
+    p.kid = v4 ? LEDN_PYR_GENERIC_V4 : LEDN_PYR_GENERIC_V1;
+    p.nb = cdiv(total, 256);
+    return p;
+}
+
+int sesp_pyramid_kernel_id(const ledn_pyr_desc& d) {
+    return sesp_pyramid_validate(d) != LEDN_OK ? -1 : sesp_pyramid_plan(d).kid;
+}
+
+int sesp_pyramid_impl(const ledn_pyr_desc& d, hipStream_t s) {
+    const int rc = sesp_pyramid_validate(d);
+    if (rc != LEDN_OK) return rc;
+    const DwPlan p = sesp_pyramid_plan(d);
+    if (p.kid < 0) return LEDN_EINVAL;
+    if (p.kid == LEDN_PYR_BF16 || p.kid == LEDN_PYR_BF16_SAME) return pyr_fwd_bf16(d, p, s);
+    const dim3 grid((unsigned)p.nb);
     return with_dtype(d.dtype_x, [&](auto t) {
         using T = tag_t<decltype(t)>;
-        if (v4) LEDN_LAUNCH((sesp_pyramid_kernel<T, T, 4>), grid, dim3(256), 0, s, d);
+        if (p.kid == LEDN_PYR_GENERIC_V4) LEDN_LAUNCH((sesp_pyramid_kernel<T, T, 4>), grid, dim3(256), 0, s, d);
         else LEDN_LAUNCH((sesp_pyramid_kernel<T, T, 1>), grid, dim3(256), 0, s, d);
         return check_launch();
     });

@@ -419,6 +419,10 @@ template <class F> inline int with_dtype(int dt, F&& f) {
     if (dt == LEDN_BF16) return f(type_tag<bf16_t>{});
     return LEDN_EINVAL;
 }
+// with_dtype has a type for the code (what a kernel-id query answers for the codes with_dtype would refuse)
+inline bool dtype_known(int dt) {
+    return with_dtype(dt, [](auto) { return LEDN_OK; }) == LEDN_OK;
+}
 template <class F> inline int with_dtypes(int dx, int dy, F&& f) {
     return with_dtype(dx, [&](auto tx) { return with_dtype(dy, [&](auto ty) { return f(tx, ty); }); });
 }
@@ -439,6 +443,19 @@ inline float* ws_take(long nfloats) {
     Workspace& w = workspace();
     return (w.ptr && nfloats <= w.nfloats) ? w.ptr : nullptr;
 }
+// What a depthwise / pyramid launcher is going to do with a descriptor: the kernel instance (the LEDN_DW_* / LEDN_DWBD_* /
+// LEDN_DWBW_* / LEDN_PYR_* / LEDN_PYRBW_* value of ledn.h), its grid and the partial rows of its reduction.  Every such
+// launcher asks its *_plan function and launches what the plan names; the ledn_*_kernel_id queries return the same plan's
+// kernel and ending, so a query cannot drift from its launcher.
+struct DwPlan {
+    int kid = -1;           // -1: no kernel takes the descriptor (LEDN_EINVAL)
+    long nb = 0;            // workgroups (grid.x)
+    long rows = 0;          // partial rows finish_partials sums
+    long ppb = 0;           // pixels per workgroup, where the kernel takes it as an argument
+    float* part = nullptr;  // the partial rows; nullptr: the atomic ending (reduce = true) or nothing to reduce
+    bool reduce = false;    // the launch ends in a cross-workgroup reduction (statistics, weight gradient)
+    int ending() const { return !reduce ? 0 : part ? LEDN_END_PARTIAL : LEDN_END_ATOMIC; }
+};
 // launch-shape knobs (ledn_set_option)
 struct Options {
     int conv_workgroups;

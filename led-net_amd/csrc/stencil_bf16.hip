@@ -92,13 +92,14 @@ __global__ void __launch_bounds__(256) dw3x3_bwd_weight_bf16_kernel(ledn_dwbwd_d
     }
 }
 
-int dw3x3_bwd_weight_bf16(const ledn_dwbwd_desc& d, hipStream_t s) {
+// the vectorised 3x3 weight gradient takes d (LEDN_DWBW_BF16_3X3): grid and ending
+bool dw3x3_bwd_weight_bf16_plan(const ledn_dwbwd_desc& d, DwPlan* p) {   // used by backward.hip
     const int cvn = d.C / 8;
     if (d.dtype != LEDN_BF16 || d.KH != 3 || d.KW != 3 || d.stride != 1 || d.ext1 || d.C % 8 || d.group_size % 8 ||
         !pow2(cvn) || cvn > 64 || d.Ho != d.H || d.Wo != d.W || (long)d.N * d.H * d.W * d.C >= (1L << 31))
-        return -1;
+        return false;
     for (int g = 0; g * d.group_size < d.C; ++g)
-        if (d.pad >= 0 && d.pad != d.dil[g]) return -1;
+        if (d.pad >= 0 && d.pad != d.dil[g]) return false;
     const int rows = 256 / cvn;
     // 16 pixels per thread (512 workgroups at 16 x 128 x 128 x 64): 28.8 / 36.6 us against 34.0 / 39.7 with 8 (graph replay,
     // r03); 32 and 64 are slower again.  Cost experiments of the same visit: every tap reading the centre pixel, only one tap
@@ -108,9 +109,16 @@ int dw3x3_bwd_weight_bf16(const ledn_dwbwd_desc& d, hipStream_t s) {
     if (nb > 1024) nb = 1024;
     float* part = (nb > 32 || det()) ? ws_take(nb * 9 * d.C) : nullptr;
     if (!part && nb > 128) nb = 128;
-    LEDN_LAUNCH(dw3x3_bwd_weight_bf16_kernel, dim3((unsigned)nb), dim3(256), (size_t)(36 * d.C) * sizeof(float), s, d,
-                part);
-    if (part) return finish_partials(part, (int)nb, 9 * d.C, 1, d.dw, nullptr, nullptr, s);
+    p->kid = LEDN_DWBW_BF16_3X3;
+    p->nb = p->rows = nb;
+    p->part = part;
+    return true;
+}
+
+int dw3x3_bwd_weight_bf16(const ledn_dwbwd_desc& d, const DwPlan& p, hipStream_t s) {   // used by backward.hip
+    LEDN_LAUNCH(dw3x3_bwd_weight_bf16_kernel, dim3((unsigned)p.nb), dim3(256), (size_t)(36 * d.C) * sizeof(float), s, d,
+                p.part);
+    if (p.part) return finish_partials(p.part, (int)p.rows, 9 * d.C, 1, d.dw, nullptr, nullptr, s);
     return check_launch();
 }
 
@@ -182,18 +190,26 @@ __global__ void __launch_bounds__(256) pyr_fwd_bf16_kernel(ledn_pyr_desc d) {
     }
 }
 
-int pyr_fwd_bf16(const ledn_pyr_desc& d, hipStream_t s) {
+// the vectorised forward takes d: LEDN_PYR_BF16_SAME (four equal dilations) or LEDN_PYR_BF16
+bool pyr_fwd_bf16_plan(const ledn_pyr_desc& d, DwPlan* p) {   // used by dwconv.hip
     const int cvn = d.n / 8;
     if (d.dtype_x != LEDN_BF16 || d.dtype_y != LEDN_BF16 || d.n % 8 || 256 % cvn || cvn > 256 ||
         (long)d.N * d.H * d.W * d.n * 4 >= (1L << 31))
-        return -1;
+        return false;
     const int rows = 256 / cvn;
     long nb = cdiv((long)d.N * d.Ho * d.Wo, rows * 2);
     if (nb > 2048) nb = 2048;
-    if (d.dil[0] == d.dil[1] && d.dil[1] == d.dil[2] && d.dil[2] == d.dil[3])
-        LEDN_LAUNCH(pyr_fwd_bf16_kernel<true>, dim3((unsigned)nb), dim3(256), (size_t)(36 * d.n) * sizeof(float), s, d);
+    p->kid = (d.dil[0] == d.dil[1] && d.dil[1] == d.dil[2] && d.dil[2] == d.dil[3]) ? LEDN_PYR_BF16_SAME : LEDN_PYR_BF16;
+    p->nb = nb;
+    return true;
+}
+
+int pyr_fwd_bf16(const ledn_pyr_desc& d, const DwPlan& p, hipStream_t s) {   // used by dwconv.hip
+    const dim3 grid((unsigned)p.nb);
+    if (p.kid == LEDN_PYR_BF16_SAME)
+        LEDN_LAUNCH(pyr_fwd_bf16_kernel<true>, grid, dim3(256), (size_t)(36 * d.n) * sizeof(float), s, d);
     else
-        LEDN_LAUNCH(pyr_fwd_bf16_kernel<false>, dim3((unsigned)nb), dim3(256), (size_t)(36 * d.n) * sizeof(float), s, d);
+        LEDN_LAUNCH(pyr_fwd_bf16_kernel<false>, grid, dim3(256), (size_t)(36 * d.n) * sizeof(float), s, d);
     return check_launch();
 }
 
@@ -529,12 +545,15 @@ __global__ void __launch_bounds__(256) pyr_bwd_data_bf16_kernel(ledn_pyrbwd_desc
     }
 }
 
-int pyr_bwd_data_bf16(const ledn_pyrbwd_desc& d, hipStream_t s) {   // gsum already holds the suffix sums
+bool pyr_bwd_data_bf16_applies(const ledn_pyrbwd_desc& d) {   // also read by pyr_bwd_data_kernel_id (backward.hip)
     const int cvn = d.n / 8;
-    if (d.dtype != LEDN_BF16 || d.stride != 1 || d.n % 8 || 256 % cvn || cvn > 256 ||
-        (long)d.N * d.H * d.W * d.n * 4 >= (1L << 31))
-        return -1;
-    const int rows = 256 / cvn;
+    return !(d.dtype != LEDN_BF16 || d.stride != 1 || d.n % 8 || 256 % cvn || cvn > 256 ||
+             (long)d.N * d.H * d.W * d.n * 4 >= (1L << 31));
+}
+
+int pyr_bwd_data_bf16(const ledn_pyrbwd_desc& d, hipStream_t s) {   // gsum already holds the suffix sums
+    if (!pyr_bwd_data_bf16_applies(d)) return -1;
+    const int rows = 256 / (d.n / 8);
     long nb = cdiv((long)d.N * d.H * d.W, rows * 2);
     if (nb > 2048) nb = 2048;
     LEDN_LAUNCH(pyr_bwd_data_bf16_kernel, dim3((unsigned)nb), dim3(256), (size_t)(36 * d.n) * sizeof(float), s, d);
@@ -724,10 +743,11 @@ __global__ void __launch_bounds__(256, 2) pyr_bwd_weight_same_kernel(ledn_pyrbwd
     }
 }
 
-int pyr_bwd_weight_bf16(const ledn_pyrbwd_desc& d, hipStream_t s) {
+// the vectorised weight gradients take d: LEDN_PYRBW_SAME, LEDN_PYRBW_BF16_FROM_DY or LEDN_PYRBW_BF16, grid and ending
+bool pyr_bwd_weight_bf16_plan(const ledn_pyrbwd_desc& d, DwPlan* p) {   // used by backward.hip
     const int cvn = d.n / 8;
     if (d.dtype != LEDN_BF16 || d.n % 8 || !pow2(cvn) || cvn > 64 || (long)d.N * d.H * d.W * d.n * 4 >= (1L << 31))
-        return -1;
+        return false;
     const int rows = 256 / cvn;
     static const bool same_on = exp_knob("LEDN_PYR_WGRAD_SAME", 1) != 0;     // (A/B knob)
     if (same_on && pyr_tile_applies(d) && d.n <= 64 && d.dil[1] == d.dil[0] && d.dil[2] == d.dil[0] && d.dil[3] == d.dil[0]) {
@@ -736,18 +756,29 @@ int pyr_bwd_weight_bf16(const ledn_pyrbwd_desc& d, hipStream_t s) {
         if (nb4 > 512) nb4 = 512;            // one resident round: two workgroups per CU by the registers
         float* part4 = (nb4 > 32 || det()) ? ws_take(nb4 * 36 * d.n) : nullptr;
         if (!part4 && nb4 > 128) nb4 = 128;
-        LEDN_LAUNCH(pyr_bwd_weight_same_kernel, dim3((unsigned)nb4), dim3(256), (size_t)(144 * d.n) * sizeof(float), s, d,
-                    part4);
-        if (part4) return finish_partials(part4, (int)nb4, 36 * d.n, 1, d.dw, nullptr, nullptr, s);
-        return check_launch();
+        p->kid = LEDN_PYRBW_SAME;
+        p->nb = p->rows = nb4;
+        p->part = part4;
+        return true;
     }
     long nb = cdiv((long)d.N * d.Ho * d.Wo, rows * 8);
     if (nb > 512) nb = 512;
     float* part = (nb > 32 || det()) ? ws_take(nb * 36 * d.n) : nullptr;
     if (!part && nb > 128) nb = 128;
-    LEDN_LAUNCH(pyr_bwd_weight_bf16_kernel, dim3((unsigned)nb, 4u), dim3(256), (size_t)(36 * d.n) * sizeof(float), s, d,
-                part, pyr_from_dy(d));
-    if (part) return finish_partials(part, (int)nb, 36 * d.n, 1, d.dw, nullptr, nullptr, s);
+    p->kid = pyr_from_dy(d) ? LEDN_PYRBW_BF16_FROM_DY : LEDN_PYRBW_BF16;
+    p->nb = p->rows = nb;
+    p->part = part;
+    return true;
+}
+
+int pyr_bwd_weight_bf16(const ledn_pyrbwd_desc& d, const DwPlan& p, hipStream_t s) {   // used by backward.hip
+    if (p.kid == LEDN_PYRBW_SAME)
+        LEDN_LAUNCH(pyr_bwd_weight_same_kernel, dim3((unsigned)p.nb), dim3(256), (size_t)(144 * d.n) * sizeof(float), s, d,
+                    p.part);
+    else
+        LEDN_LAUNCH(pyr_bwd_weight_bf16_kernel, dim3((unsigned)p.nb, 4u), dim3(256), (size_t)(36 * d.n) * sizeof(float), s, d,
+                    p.part, p.kid == LEDN_PYRBW_BF16_FROM_DY);
+    if (p.part) return finish_partials(p.part, (int)p.rows, 36 * d.n, 1, d.dw, nullptr, nullptr, s);
     return check_launch();
 }
 

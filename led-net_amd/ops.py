@@ -518,10 +518,15 @@ def conv2d_wgrad(x, dz, w_shape, *, stride=1, pad=0, dil=1, groups=1, xadd=None,
     return dw, db
 
 
-def dwconv2d(x, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_size=None, out_scale=None,
-             out_shift=None, act=ACT_NONE, slope=None, stats=None, ext1=False, out_dtype=None, defer_stats=False):
-    """Depthwise conv.  x: [N,H,W,C]; w_khwc: [KH,KW,C] f32."""
-    lib = _lib.get_lib()
+def _query(lib, name, ref, d):
+    """a ledn_*_kernel_id query (no launch) for the stream and workspace _run would hand the entry itself"""
+    stream = _stream(lib, ref)
+    lib.ensure_workspace(ref.device, _slot(ref) if lib.is_hip else 0, stream=stream)
+    return int(getattr(lib.cdll, name)(d, stream))
+
+
+def _dwconv_desc(lib, x, w_khwc, stride, pad, dil, group_size, out_scale, out_shift, act, slope, stats, ext1, out_dtype):
+    """-> (ledn_dw_desc, y) of dwconv2d's arguments"""
     N, H, W, Cc = x.shape
     KH, KW, Cw = w_khwc.shape
     if Cw != Cc:
@@ -546,13 +551,46 @@ def dwconv2d(x, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_size=None, 
         d.dil[i] = dil[i] if i < len(dil) else dil[-1]
     d.group_size, d.act_out, d.ext1 = group_size, act, int(ext1)
     d.dtype_x, d.dtype_y = _dt(x), _dt(y)
+    return d, y
+
+
+# include/ledn.h LEDN_DW_*: index = ledn_dwconv2d_kernel_id(...) & KERNEL_MASK
+KERNEL_MASK, END_ATOMIC, END_PARTIAL = 0xff, 0x100, 0x200
+DW_KERNELS = ('dwconv_kernel<1,0>', 'dwconv_kernel<4,0>', 'dwconv_kernel<4,9>', 'dw3x3_bf16_kernel<0>',
+              'dw3x3_tile_kernel<0,2,16,false>', 'dw3x3_tile_kernel<0,2,16>', 'dw3x3_tile_kernel<0,2,8>',
+              'dw3x3_tile_kernel<0,5,8,false>', 'dw3x3_tile_kernel<0,5,8>', 'dw8x8_tile_kernel<0>')
+PYR_KERNELS = ('sesp_pyramid_kernel<1>', 'sesp_pyramid_kernel<4>', 'pyr_fwd_bf16_kernel<false>', 'pyr_fwd_bf16_kernel<true>')
+
+
+def kernel_name(table, kid):
+    """'name' or 'name+atomic' / 'name+partial' of a ledn_*_kernel_id value (None for -1: the entry would refuse)"""
+    if kid < 0:
+        return None
+    return table[kid & KERNEL_MASK] + {0: '', END_ATOMIC: '+atomic', END_PARTIAL: '+partial'}[kid & ~KERNEL_MASK]
+
+
+def dwconv2d_kernel_id(x, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_size=None, out_scale=None,
+                       out_shift=None, act=ACT_NONE, slope=None, stats=None, ext1=False, out_dtype=None):
+    """ledn_dwconv2d_kernel_id for dwconv2d's arguments (no launch): kernel_name(DW_KERNELS, .) names the instance
+    and the ending of its statistics under the current options, deterministic mode and workspace"""
+    lib = _lib.get_lib()
+    d, _ = _dwconv_desc(lib, x, w_khwc, stride, pad, dil, group_size, out_scale, out_shift, act, slope, stats, ext1, out_dtype)
+    return _query(lib, 'ledn_dwconv2d_kernel_id', x, d)
+
+
+def dwconv2d(x, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_size=None, out_scale=None,
+             out_shift=None, act=ACT_NONE, slope=None, stats=None, ext1=False, out_dtype=None, defer_stats=False):
+    """Depthwise conv.  x: [N,H,W,C]; w_khwc: [KH,KW,C] f32."""
+    lib = _lib.get_lib()
+    d, y = _dwconv_desc(lib, x, w_khwc, stride, pad, dil, group_size, out_scale, out_shift, act, slope, stats, ext1, out_dtype)
+    N, H, W, Cc = x.shape
+    KH, KW, _ = w_khwc.shape
     _run_stats(lib, 'ledn_dwconv2d', x, stats, defer_stats, d, work=_TIMING is not None and (f'dw{KH}x{KW} C{Cc} s{stride} {N}x{H}x{W}', _nb(x, y, w_khwc), 2 * y.numel() * KH * KW))
     return y
 
 
-def sesp_pyramid(x, w_b33n, dil, stride):
-    """x: [N,H,W,n]; w: [4,3,3,n] f32 -> [N,Ho,Wo,4n] (cat layout, HFF sums applied)."""
-    lib = _lib.get_lib()
+def _pyr_desc(lib, x, w_b33n, dil, stride):
+    """-> (ledn_pyr_desc, y) of sesp_pyramid's arguments"""
     N, H, W, n = x.shape
     if tuple(w_b33n.shape) != (4, 3, 3, n):
         raise LednError('sesp_pyramid: weight shape')
@@ -565,6 +603,21 @@ def sesp_pyramid(x, w_b33n, dil, stride):
     for i in range(4):
         d.dil[i] = dil[i]
     d.dtype_x = d.dtype_y = _dt(x)
+    return d, y
+
+
+def sesp_pyramid_kernel_id(x, w_b33n, dil, stride):
+    """ledn_sesp_pyramid_kernel_id for sesp_pyramid's arguments (no launch): index into PYR_KERNELS"""
+    lib = _lib.get_lib()
+    d, _ = _pyr_desc(lib, x, w_b33n, dil, stride)
+    return _query(lib, 'ledn_sesp_pyramid_kernel_id', x, d)
+
+
+def sesp_pyramid(x, w_b33n, dil, stride):
+    """x: [N,H,W,n]; w: [4,3,3,n] f32 -> [N,Ho,Wo,4n] (cat layout, HFF sums applied)."""
+    lib = _lib.get_lib()
+    d, y = _pyr_desc(lib, x, w_b33n, dil, stride)
+    N, H, W, n = x.shape
     _run(lib, 'ledn_sesp_pyramid', x, d, work=_TIMING is not None and (f'pyr n{n} s{stride} {N}x{H}x{W}', _nb(x, y, w_b33n), 2 * y.numel() * 9))
     return y
 

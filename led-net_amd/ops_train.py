@@ -264,6 +264,25 @@ def dwconv2d_bwd_fused_applies(x, dz, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1,
     return bool(_lib.get_lib().cdll.ledn_dwconv2d_bwd_fused_applies(d))
 
 
+# include/ledn.h LEDN_DWBD_* / LEDN_DWBW_* / LEDN_PYRBW_*: index = kernel id & ops.KERNEL_MASK (ops.kernel_name)
+DW_BWD_DATA_KERNELS = ('dw_bwd_data_kernel<1>', 'dw_bwd_data_kernel<4>', 'dw3x3_bf16_kernel<1>', 'dw3x3_tile_kernel<1,2,16>',
+                       'dw3x3_tile_kernel<1,2,8>', 'dw3x3_tile_kernel<1,5,8>', 'dw8x8_tile_kernel<1>')
+DW_BWD_WEIGHT_KERNELS = ('dw_bwd_weight_kernel<1>', 'dw_bwd_weight_kernel<4>', 'dw_bwd_weight_row_kernel<4,8>',
+                         'dw_bwd_weight3x3_kernel<4>', 'dw3x3_bwd_weight_bf16_kernel', 'dw8x8_wgrad_tile_kernel')
+PYR_BWD_WEIGHT_KERNELS = ('pyr_bwd_weight_kernel<1>', 'pyr_bwd_weight_kernel<4>', 'pyr_bwd_weight_bf16_kernel',
+                          'pyr_bwd_weight_bf16_kernel<from_dy>', 'pyr_bwd_weight_same_kernel')
+
+
+def dwconv2d_bwd_kernel_ids(x, dz, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_size=None, ext1=False):
+    """(ledn_dwconv2d_bwd_data_kernel_id, ledn_dwconv2d_bwd_weight_kernel_id) for dwconv2d_bwd's operands (no launch):
+    indices into DW_BWD_DATA_KERNELS / DW_BWD_WEIGHT_KERNELS, the second with the ending of its reduction OR-ed in"""
+    lib = _lib.get_lib()
+    d = _dw_desc(x.shape, dz, w_khwc, stride, pad, dil, group_size, ext1, _dt(x))
+    d.x, d.dz, d.w, d.dx, d.dw = _p(x), _p(dz), _p(_f32(w_khwc)), _p(x), _p(w_khwc)      # only tested for NULL
+    return (_ops._query(lib, 'ledn_dwconv2d_bwd_data_kernel_id', x, d),
+            _ops._query(lib, 'ledn_dwconv2d_bwd_weight_kernel_id', x, d))
+
+
 def dwconv2d_bwd(x, dz, w_khwc, *, stride=1, pad=-1, dil=(1, 1, 1, 1), group_size=None, ext1=False,
                  add=None, need_dx=True, need_dw=True, dw_out=None):
     """-> (dx or None, dw [KH,KW,C] or None)."""
@@ -367,6 +386,20 @@ def sesp_pyramid_bwd_kernel_id(x, dy, dil, stride):
         d.dil[i] = dil[i]
     d.dtype = _dt(x)
     return int(lib.cdll.ledn_sesp_pyramid_bwd_kernel_id(d))
+
+
+def sesp_pyramid_bwd_weight_kernel_id(x, dy, dil, stride):
+    """which kernel ledn_sesp_pyramid_bwd_weight runs these arguments on and how its reduction ends (no launch): index
+    into PYR_BWD_WEIGHT_KERNELS with the ending OR-ed in (ops.kernel_name)"""
+    lib = _lib.get_lib()
+    d = _lib.PyrBwdDesc()
+    N, H, W, n = x.shape
+    d.x, d.dy, d.gsum, d.dx, d.dw = _p(x), _p(dy), _p(dy), _p(x), _p(x)     # only tested for NULL
+    d.N, d.H, d.W, d.n, d.Ho, d.Wo, d.stride = N, H, W, n, dy.shape[1], dy.shape[2], stride
+    for i in range(4):
+        d.dil[i] = dil[i]
+    d.dtype = _dt(x)
+    return _ops._query(lib, 'ledn_sesp_pyramid_bwd_weight_kernel_id', x, d)
 
 
 def sesp_pyramid_bwd(x, dy, w_b33n, dil, stride, dw_out=None):
