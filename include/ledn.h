@@ -72,7 +72,13 @@ enum {
     LEDN_OPT_DW_BWD_WORKGROUPS = 5, /* persistent workgroups of the fused depthwise 3x3 backward (ledn_dwconv2d_bwd), shared
                                        out over the 32-channel slices and capped at 256 per slice (default 512: two resident
                                        per CU) */
-    LEDN_OPT_DETERMINISTIC = 3      /* 1: every cross-workgroup reduction of the library (BatchNorm statistics and their
+    LEDN_OPT_S2_DGRAD = 6,          /* 1 (default): the data gradient of the 3x3 stride-2 convolutions runs as four parity
+                                       sub-convolutions (conv_s2dgrad_mfma_kernel: only the taps that meet a dz pixel);
+                                       0: as a stride-1 correlation over the zero-upsampled dz (conv_mfma_kernel, three
+                                       of four staged pixels zero; A/B measurements); < 0: the default.  The two forms
+                                       differ by f32 summation order only.  ledn_conv2d_s2_dgrad_applies tells which
+                                       descriptors the option concerns */
+    LEDN_OPT_DETERMINISTIC = 3     /* 1: every cross-workgroup reduction of the library (BatchNorm statistics and their
                                        backward sums, weight / bias gradients, pooled contexts and their gradients, the
                                        attention's bias gradient and the gradients of reflect-padded windows) runs in a
                                        FIXED order: per-workgroup partial rows in the bound workspace + an ordered summing
@@ -146,6 +152,11 @@ int ledn_stats_defer_end(float** part, int* rows);
  * conv_direct_kernel / conv_narrowin_kernel (VALU).  bench.py names the kernel in its
  * roofline with it. */
 int ledn_conv2d_uses_mfma(const ledn_conv_desc* d);
+/* Pure query, no launch: 1 if ledn_conv2d would run this descriptor on conv_s2dgrad_mfma_kernel (the parity form of the
+ * 3x3 stride-2 data gradient, csrc/conv_mfma.hip): ledn_conv2d_uses_mfma(d) == 1, transposed, 3x3, stride 2, pad 1, bf16
+ * output, Cout % 8 == 0, no input prologue / output affine / activation / statistics, res_mode none or LEDN_RES_ADD, and
+ * LEDN_OPT_S2_DGRAD on; 0 otherwise (such descriptors stay on conv_mfma_kernel's zero-upsampled form). */
+int ledn_conv2d_s2_dgrad_applies(const ledn_conv_desc* d);
 
 /* bf16 weight pack for the MFMA path, from the OIHW f32 master [Cout][Cin/groups][KH][KW]
  * (Cin = full input width; a grouped 1x1 is densified: zeros outside its group):

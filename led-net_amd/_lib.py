@@ -20,6 +20,7 @@ ACT_NONE, ACT_RELU, ACT_RELU6, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3, 4
 RES_NONE, RES_ADD, RES_GATE = 0, 1, 2
 OPT_CONV_WORKGROUPS, OPT_WGRAD_WORKGROUPS, OPT_STREAM_FAST, OPT_DETERMINISTIC, OPT_BN_FUSED = 0, 1, 2, 3, 4
 OPT_DW_BWD_WORKGROUPS = 5
+OPT_S2_DGRAD = 6
 ESKIP = 3
 
 vp, fp, i32, i64 = C.c_void_p, C.c_void_p, C.c_int, C.c_longlong
@@ -275,6 +276,7 @@ _PROTOS = {
     'ledn_set_option': ([i32, i64], i32),
     'ledn_conv2d': ([C.POINTER(ConvDesc), vp], i32),
     'ledn_conv2d_uses_mfma': ([C.POINTER(ConvDesc)], i32),
+    'ledn_conv2d_s2_dgrad_applies': ([C.POINTER(ConvDesc)], i32),
     'ledn_stats_defer_begin': ([], i32),
     'ledn_stats_defer_end': ([C.POINTER(C.c_void_p), C.POINTER(i32)], i32),
     'ledn_conv2d_deferred_stats': ([C.POINTER(ConvDesc), C.POINTER(C.c_void_p), C.POINTER(i32), vp], i32),

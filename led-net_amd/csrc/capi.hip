@@ -11,6 +11,7 @@ int conv_f32_mfma(const ledn_conv_desc& d, hipStream_t s);
 bool conv_wgrad_f32_mfma_supported(const ledn_wgrad_desc& d);
 int conv_wgrad_f32_mfma(const ledn_wgrad_desc& d, hipStream_t s);
 int conv_mfma(const ledn_conv_desc& d, hipStream_t s);
+bool conv_s2dgrad_applies(const ledn_conv_desc& d);
 int conv_wgrad_mfma_partial(const ledn_wgrad_desc& d, float* part, long long part_floats, ledn_wgrad_finish_entry* entry,
                             bool query, hipStream_t s);
 int conv_wgrad_finish_multi_impl(const ledn_wgrad_finish_entry* table_dev, int n, int total_chunks, hipStream_t s);
@@ -196,7 +197,7 @@ static hipStream_t enter_stream(void* stream) {         // every extern "C" entr
     return (hipStream_t)stream;
 }
 Workspace& workspace() { return tls_ws; }
-static Options g_opt = {512, 512, 91, 0, 0, 512};   // stream_fast: bit 0 BatchNorm / affine streaming kernels, bit 1 LDS-tiled depthwise 3x3, bit 2 round-robin conv tiles (off), bit 3 8-row conv tiles for under-filled grids, bit 4 register-direct 1x1 conv (conv1x1.hip), bit 5 resident 3x3 weights for 32 < Cin <= 64 (off: measured slower, r3l), bit 6 register-direct 3x3 conv for 32 input channels (conv3x3.hip)
+static Options g_opt = {512, 512, 91, 0, 0, 512, 1};   // stream_fast: bit 0 BatchNorm / affine streaming kernels, bit 1 LDS-tiled depthwise 3x3, bit 2 round-robin conv tiles (off), bit 3 8-row conv tiles for under-filled grids, bit 4 register-direct 1x1 conv (conv1x1.hip), bit 5 resident 3x3 weights for 32 < Cin <= 64 (off: measured slower, r3l), bit 6 register-direct 3x3 conv for 32 input channels (conv3x3.hip)
 Options& options() { return g_opt; }
 static thread_local DeferredStats g_defer = {false, nullptr, 0};
 DeferredStats& deferred_stats() { return g_defer; }
@@ -235,6 +236,7 @@ int ledn_set_option(int option, long long value) {
         case LEDN_OPT_DETERMINISTIC: options().deterministic = value > 0 ? 1 : 0; return LEDN_OK;
         case LEDN_OPT_BN_FUSED: options().bn_fused = value > 0 ? 1 : 0; return LEDN_OK;
         case LEDN_OPT_DW_BWD_WORKGROUPS: options().dw_bwd_workgroups = value > 0 ? (int)value : 512; return LEDN_OK;
+        case LEDN_OPT_S2_DGRAD: options().s2_dgrad = value != 0 ? 1 : 0; return LEDN_OK;   // (< 0: the default, 1)
         default: return LEDN_EINVAL;
     }
 }
@@ -305,6 +307,9 @@ int ledn_conv2d_uses_mfma(const ledn_conv_desc* d) {
     if (d && !conv_mfma_supported(*d) && conv_validate(*d) == LEDN_OK && conv_f32_mfma_supported(*d)) return 5;
     if (!d || !conv_mfma_supported(*d)) return 0;
     return conv1x1_reg_supported(*d) ? 2 : (conv3x3_reg_supported(*d) ? 3 : 1);
+}
+int ledn_conv2d_s2_dgrad_applies(const ledn_conv_desc* d) {
+    return d && conv_validate(*d) == LEDN_OK && ledn_conv2d_uses_mfma(d) == 1 && conv_s2dgrad_applies(*d) ? 1 : 0;
 }
 int ledn_conv2d_wgrad_uses_mfma(const ledn_wgrad_desc* d) {
     if (d && wgrad_validate(*d) == LEDN_OK && !conv_wgrad_cout2_supported(*d) && head_mc_wgrad_supported(*d)) return 5;

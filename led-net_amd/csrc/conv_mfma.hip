@@ -21,7 +21,9 @@
 //   tile goes through a per-wave LDS transposition so that global stores are 16 B per lane and
 //   cover whole 64-byte channel rows.
 //   Data gradient = the same kernel: stride-1 convs use the flipped/transposed weight pack;
-//   stride-2 convs read dz as a zero-upsampled patch (UP = 2).
+//   3x3 stride-2 convs run as four parity sub-convolutions on conv_s2dgrad_mfma_kernel (below; LEDN_OPT_S2_DGRAD);
+//   with that option off, with a prologue / affine / activation, and for 1x1 stride 2, dz is read as a zero-upsampled
+//   patch (UP = 2).
 //   The hot loop is kept small on purpose (~30 KB of code): the first unrolled version was 90 KB and
 //   ran instruction-cache bound.
 //
@@ -712,6 +714,266 @@ static int launch_shape(const MfmaConvArgs& a, hipStream_t s) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Data gradient of the 3x3 / stride-2 / pad-1 convolutions as four parity sub-convolutions (conv_s2dgrad_mfma_kernel)
+//   With the flipped pack [f][ci_f][co_f] (f = 8 - tap, fh = f / 3, fw = f % 3):
+//     dx[n, 2a+ph, 2b+pw, ci] = sum over fh in F(ph), fw in F(pw), co of pack[fh*3+fw][ci][co] * dz[n, a + fh/2, b + fw/2, co]
+//     F(0) = {1}, F(1) = {0, 2}; dz rows >= H and columns >= W read as zero.
+//   The zero-upsampled form (conv_mfma_kernel with UP = 2) stages, reads and multiplies three zero pixels for every dz
+//   pixel; here only the 1 + 2 + 2 + 4 = 9 products per (a, b) that are not zero are issued.
+//   Workgroup = 4 wavefronts = TA = 4 * MT rows of a x 32 columns of b x 32 dx channels (2 TA x 64 output pixels).  The
+//   staged patch is the (TA + 1) x 33 dz pixels of one 32-channel K-chunk (halo below and to the right only).  A wave owns
+//   MT rows of a and four accumulator tiles per row, one per parity class (ph, pw).  Per 16-channel k-step it reads the
+//   2 (MT + 1) pixel fragments of its rows (column shifts 0 / 1; the shift-1 row of a-row m is the shift-0 row of m + 1)
+//   and nine weight fragments, and issues 9 MT matrix instructions.  Persistent workgroups, (tile, K-chunk) steps and the
+//   load / commit / MFMA pipeline are those of conv_mfma_kernel.
+//   Epilogue: the lane holds pixel b of both pw classes and 4 x 4 channels; v_permlane32_swap between the two classes
+//   leaves lane (lr, lh) with ALL 32 channels of output pixel 2 b + lh, and a 4 x 4 transposition of the 16-byte pieces
+//   inside every lane quad makes four consecutive lanes store the 64 contiguous bytes of ONE pixel (per store
+//   instruction; with every lane storing its own pixel's piece q, 16 bytes at a 64-byte stride, the stem layer ran at
+//   111 - 131 us instead of 88 - 92).  Flavours: EPI_RAW and EPI_RAW_ACC (bf16 addend read as the same 16-byte
+//   pieces).  Every output element is written exactly once: no atomics, nothing for deterministic mode to order.
+// ---------------------------------------------------------------------------
+constexpr int s2_tap_order(int j) {   // no two consecutive products (k-steps wrap around) into the same parity class
+    constexpr int o[9] = {0, 1, 2, 3, 6, 5, 8, 7, 4};
+    return o[j];
+}
+
+template <int MT, int EPI>
+__global__ void __launch_bounds__(256, 2) conv_s2dgrad_mfma_kernel(MfmaConvArgs a) {
+    static_assert(EPI == EPI_RAW || EPI == EPI_RAW_ACC, "raw epilogues only");
+    constexpr int TA = 4 * MT;
+    constexpr int PR = TA + 1, PC = 33;
+    constexpr int WROWS = 9 * 32;                           // weight rows of one K-chunk: [f][32 dx channels]
+    constexpr int NLW = (WROWS * 4 + 255) / 256;
+    __shared__ __attribute__((aligned(16))) unsigned char s_patch[PR * PC * PIXB];
+    __shared__ __attribute__((aligned(16))) unsigned char s_w[WROWS * PIXB];
+    const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
+    const int lr = lane & 31, lh = lane >> 5;
+    const int cb0 = blockIdx.y * 32;                        // first dx channel of the workgroup
+
+    const long ntiles = (long)a.N * a.tiles_h * a.tiles_w;
+    const long tstep = a.tile_stride > 0 ? a.tile_stride : 1;
+    const long tb = a.tile_stride > 0 ? (long)blockIdx.x : (long)blockIdx.x * a.tiles_per_block;
+    const long te = a.tile_stride > 0 ? ntiles : min(ntiles, tb + a.tiles_per_block);
+    if (tb >= te) return;                                   // workgroup-uniform
+    const bool one_chunk = a.Cin <= CK;                     // the only K-chunk's weights: loaded once
+
+    // weights of K-chunk c0 -> LDS (16-byte pieces; dx channels beyond Cout / dz channels beyond Cin are zero)
+    auto load_weights = [&](const int c0) {
+        uint4 wv[NLW];
+#pragma unroll
+        for (int j = 0; j < NLW; ++j) {
+            const int e = tid + j * 256, row = e >> 2, part = e & 3;
+            const int co = cb0 + (row & 31), ci = c0 + part * 8;
+            const bool ok = row < WROWS && co < a.Cout && ci < a.Cin;
+            const long off = ok ? ((long)(row >> 5) * a.Cout + co) * a.Cin + ci : 0;
+            wv[j] = *reinterpret_cast<const uint4*>(a.wp + off);
+            if (!ok) wv[j] = make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int j = 0; j < NLW; ++j) {
+            const int e = tid + j * 256;
+            if (e < WROWS * 4) *reinterpret_cast<uint4*>(s_w + (e >> 2) * PIXB + (e & 3) * 16) = wv[j];
+        }
+    };
+    PatchStage<PR, PC, 1, 1> stage;
+    auto fetch = [&](long tile, const int c0) {
+        const int tw = (int)(tile % a.tiles_w); tile /= a.tiles_w;
+        const int th = (int)(tile % a.tiles_h);
+        stage.fetch(a.x, (int)(tile / a.tiles_h), a.H, a.W, a.Cin, th * TA, tw * 32, c0, tid);
+    };
+    if (one_chunk) load_weights(0);
+
+    f32x16_t acc[MT][4];                                    // [row of a][ph * 2 + pw]
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[m][p][i] = 0.f;
+
+    auto do_step = [&](const long tile, const int c0) {
+        stage.commit(s_patch, nullptr, nullptr, nullptr, LEDN_ACT_NONE, c0, tid);
+        if (!one_chunk) load_weights(c0);
+        __syncthreads();
+        long ntile = tile;
+        int nc0 = c0 + CK;
+        if (nc0 >= a.Cin) { nc0 = 0; ntile = tile + tstep; }
+        if (ntile < te) fetch(ntile, nc0);
+        // ---- 2 k-steps x 9 taps, all operands from LDS.  The pixel fragments of a k-step (rows 0 .. MT, column shifts
+        // 0 / 1) stay in registers for its nine products; those of the next k-step and the weight fragment of the next
+        // product are read before the matrix instructions of the current product are issued.
+        constexpr int NKS = CK / 16, NXF = 2 * (MT + 1), NSTEP = 9 * NKS;
+        const unsigned char* wbase = s_w + lr * PIXB + lh * 16;
+        const unsigned char* xbase = s_patch + (long)((wm * MT) * PC + lr) * PIXB + lh * 16;
+        bf16x8_t xf[2][MT + 1][2], wf_n;
+#pragma unroll
+        for (int r = 0; r <= MT; ++r)
+#pragma unroll
+            for (int sw = 0; sw < 2; ++sw)
+                xf[0][r][sw] = *reinterpret_cast<const bf16x8_t*>(xbase + (long)(r * PC + sw) * PIXB);
+        wf_n = *reinterpret_cast<const bf16x8_t*>(wbase + s2_tap_order(0) * 32 * PIXB);
+        static_for<NSTEP>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            constexpr int kk = i / 9, j = i % 9, f = s2_tap_order(j), fh = f / 3, fw = f % 3;
+            constexpr int cls = (fh != 1 ? 2 : 0) + (fw != 1 ? 1 : 0), sh = fh / 2, sw = fw / 2;
+            const bf16x8_t wf = wf_n;
+            if constexpr (i + 1 < NSTEP)
+                wf_n = *reinterpret_cast<const bf16x8_t*>(wbase + s2_tap_order((i + 1) % 9) * 32 * PIXB + ((i + 1) / 9) * 32);
+            if constexpr (kk + 1 < NKS && j < NXF)
+                xf[(kk + 1) & 1][j / 2][j % 2] =
+                    *reinterpret_cast<const bf16x8_t*>(xbase + (long)((j / 2) * PC + (j % 2)) * PIXB + (kk + 1) * 32);
+            sched_fence();
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m][cls] = mfma_32x32x16_bf16(wf, xf[kk & 1][m + sh][sw], acc[m][cls]);
+            sched_fence();
+        });
+        __syncthreads();     // patch and chunk weights may be overwritten from here on
+
+        if (nc0 == 0) {
+            // ---- epilogue of `tile`: before the swaps the lane holds pixel (a, b0 + lr) of the four classes, register i =
+            // channel cb0 + (i&3) + 8*(i>>2) + 4*lh; after them ALL 32 channels of output pixel (2a + ph, 2 (b0 + lr) + lh)
+            long b = tile;
+            const int tw = (int)(b % a.tiles_w); b /= a.tiles_w;
+            const int th = (int)(b % a.tiles_h);
+            const int n = (int)(b / a.tiles_h);
+            // store k of a row: piece lr & 3 (8 channels) of output pixel 2 (b0 + (lr & ~3) + k) + lh, so that four
+            // consecutive lanes write the 64 contiguous bytes of one pixel's channel slice
+            const int qq = lr & 3;
+            const int wq = 2 * (tw * 32 + (lr & ~3)) + lh;
+            const bool ch_ok = cb0 + 8 * qq < a.Cout;
+            const bool b0s = lr & 1, b1s = lr & 2;
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+#pragma unroll
+                for (int ph = 0; ph < 2; ++ph) {
+                    const int ho = 2 * (th * TA + wm * MT + m) + ph;
+                    const long row = ((long)n * a.Ho + ho) * a.Wo;
+                    bool ok[4];
+                    long off[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        ok[k] = ch_ok && ho < a.Ho && wq + 2 * k < a.Wo;
+                        off[k] = (row + wq + 2 * k) * a.Cout + cb0 + 8 * qq;
+                    }
+                    uint4 radd[4];
+                    if (EPI == EPI_RAW_ACC) {       // the addend's pieces, in flight during the conversion
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) radd[k] = *reinterpret_cast<const uint4*>(a.res + (ok[k] ? off[k] : 0L));
+                    }
+                    unsigned pk[2][4][2];
+#pragma unroll
+                    for (int pw = 0; pw < 2; ++pw)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            f32x16_t& c = acc[m][ph * 2 + pw];
+                            pk[pw][q][0] = (unsigned)f32_to_bf16(c[4 * q]) | ((unsigned)f32_to_bf16(c[4 * q + 1]) << 16);
+                            pk[pw][q][1] = (unsigned)f32_to_bf16(c[4 * q + 2]) | ((unsigned)f32_to_bf16(c[4 * q + 3]) << 16);
+#pragma unroll
+                            for (int k2 = 0; k2 < 4; ++k2) c[4 * q + k2] = 0.f;
+                        }
+                    // lanes l / l + 32 hold channels 8q + {0-3} / 8q + {4-7} of pixels 2b (pk[0]) and 2b + 1 (pk[1]); after
+                    // the swaps lane l has channels 8q + 0..7 of pixel 2b, lane l + 32 those of pixel 2b + 1
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        permlane32_swap(pk[0][q][0], pk[1][q][0]);
+                        permlane32_swap(pk[0][q][1], pk[1][q][1]);
+                    }
+                    // o[q][.] = piece q of the lane's pixel; 4 x 4 transposition inside every lane quad (two butterfly
+                    // steps): o[k][.] = piece lr & 3 of the pixel of lane (lr & ~3) + k
+                    unsigned o[4][4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        o[q][0] = pk[0][q][0]; o[q][1] = pk[0][q][1]; o[q][2] = pk[1][q][0]; o[q][3] = pk[1][q][1];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; j += 2)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const unsigned recv = __shfl_xor(b0s ? o[j][e] : o[j + 1][e], 1);
+                            o[j][e] = b0s ? recv : o[j][e];
+                            o[j + 1][e] = b0s ? o[j + 1][e] : recv;
+                        }
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const unsigned recv = __shfl_xor(b1s ? o[j][e] : o[j + 2][e], 2);
+                            o[j][e] = b1s ? recv : o[j][e];
+                            o[j + 2][e] = b1s ? o[j + 2][e] : recv;
+                        }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        uint4 v = make_uint4(o[k][0], o[k][1], o[k][2], o[k][3]);
+                        if (EPI == EPI_RAW_ACC) {
+                            float fo[8], fr[8];
+                            ld8(reinterpret_cast<const bf16_t*>(&v), fo);
+                            ld8(reinterpret_cast<const bf16_t*>(&radd[k]), fr);
+#pragma unroll
+                            for (int k2 = 0; k2 < 8; ++k2) fo[k2] += fr[k2];
+                            st8(reinterpret_cast<bf16_t*>(&v), fo);
+                        }
+                        if (ok[k]) *reinterpret_cast<uint4*>(a.y + off[k]) = v;
+                    }
+                }
+            }
+        }
+    };
+    {
+        long tile = tb;
+        int c0 = 0;
+        fetch(tile, 0);
+        while (tile < te) {
+            do_step(tile, c0);
+            c0 += CK;
+            if (c0 >= a.Cin) { c0 = 0; tile += tstep; }
+        }
+    }
+}
+
+template <int MT, int EPI>
+static int launch_s2dgrad(MfmaConvArgs a, long want, hipStream_t s) {
+    constexpr int TA = 4 * MT;
+    a.tiles_h = (int)cdiv(cdiv(a.Ho, 2), TA);
+    a.tiles_w = (int)cdiv(cdiv(a.Wo, 2), 32);
+    const long ntiles = (long)a.N * a.tiles_h * a.tiles_w;
+    const long gy = cdiv(a.Cout, 32);
+    long nbx = cdiv(want, gy);
+    if (nbx > ntiles) nbx = ntiles;
+    a.tiles_per_block = (int)cdiv(ntiles, nbx);
+    nbx = cdiv(ntiles, a.tiles_per_block);
+    a.tile_stride = (options().stream_fast & 4) ? (int)nbx : 0;
+    LEDN_LAUNCH((conv_s2dgrad_mfma_kernel<MT, EPI>), dim3((unsigned)nbx, (unsigned)gy), dim3(256), 0, s, a);
+    return check_launch();
+}
+
+// ledn_conv2d_s2_dgrad_applies: conv_mfma() runs this (conv_mfma_supported) descriptor on conv_s2dgrad_mfma_kernel
+bool conv_s2dgrad_applies(const ledn_conv_desc& d) {
+    if (!options().s2_dgrad || !d.transposed || d.KH != 3 || d.KW != 3 || d.stride != 2 || d.pad != 1) return false;
+    if (d.dtype_x != LEDN_BF16 || d.dtype_y != LEDN_BF16 || (d.Cout & 7)) return false;
+    if (d.in_scale || d.in_shift || d.in_act != LEDN_ACT_NONE) return false;
+    if (d.out_scale || d.out_shift || d.act_out != LEDN_ACT_NONE || d.stat_sum) return false;
+    if (d.res_mode != LEDN_RES_NONE && !(d.res_mode == LEDN_RES_ADD && d.res)) return false;
+    return (long)d.H * d.W * d.Cin < (1L << 31);             // PatchStage: 32-bit element offsets inside one image
+}
+
+// Tile height (measured on the three layers of the 1024 x 1024 step, profiles/s2_dgrad_bench.txt):
+//   one K-chunk (dz channels <= 32: the stem layer, 335 - 600 MB per launch) is bound by memory, not by the matrix phase:
+//     MT = 1, whose 154 registers and 36 KB of LDS let THREE workgroups share a CU -- 1.5 x the workgroups wanted
+//     (with addend 122 us against 140 us for MT = 2 at two per CU);
+//   fewer 8-row tiles than workgroups wanted (the 1/16-resolution layer): MT = 1 doubles the parallelism, as bit 3 of the
+//     stream-fast mask does for the stride-1 launches (23.3 against 25.5 us);
+//   otherwise MT = 2 (128 -> 64 at 1/8 resolution: 23.0 against 26.0 us).
+static int conv_s2dgrad(const ledn_conv_desc& d, const MfmaConvArgs& a, hipStream_t s) {
+    const bool acc = d.res_mode == LEDN_RES_ADD;
+    const long want = options().conv_workgroups;             // default ~2 resident workgroups per CU
+    if (d.Cin <= CK) return acc ? launch_s2dgrad<1, EPI_RAW_ACC>(a, want + want / 2, s) : launch_s2dgrad<1, EPI_RAW>(a, want + want / 2, s);
+    const bool small = (long)d.N * cdiv(cdiv(d.Ho, 2), 8) * cdiv(cdiv(d.Wo, 2), 32) * cdiv(d.Cout, 32) < want;
+    if (small) return acc ? launch_s2dgrad<1, EPI_RAW_ACC>(a, want, s) : launch_s2dgrad<1, EPI_RAW>(a, want, s);
+    return acc ? launch_s2dgrad<2, EPI_RAW_ACC>(a, want, s) : launch_s2dgrad<2, EPI_RAW>(a, want, s);
+}
+
 bool conv_mfma_supported(const ledn_conv_desc& d) {
     if (!d.w_bf16 || d.dtype_x != LEDN_BF16) return false;
     // f32 output: narrow heads only (scalar-store epilogue), no residual (it would be f32 too)
@@ -742,6 +1004,7 @@ int conv_mfma(const ledn_conv_desc& d, hipStream_t s) {
         return d.stride == 1 ? launch_shape<1, 1, 1>(a, s) : launch_shape<1, 2, 1>(a, s);
     }
     a.pad = d.KH - 1 - d.pad;   // stride-1 correlation over the (zero-upsampled) dz with flipped taps
+    if (conv_s2dgrad_applies(d)) return conv_s2dgrad(d, a, s);   // 3x3 stride 2: parity sub-convolutions (LEDN_OPT_S2_DGRAD)
     if (d.KH == 3) return d.stride == 1 ? launch_shape<3, 1, 1>(a, s) : launch_shape<3, 1, 2>(a, s);
     // 1x1 stride 2: a 1x1 correlation over the zero-upsampled dz (three of four outputs are zero)
     return d.stride == 1 ? launch_shape<1, 1, 1>(a, s) : launch_shape<1, 1, 2>(a, s);

@@ -464,6 +464,7 @@ struct Options {
     int deterministic;      // LEDN_OPT_DETERMINISTIC: every cross-workgroup reduction in a fixed order (no f32 atomics)
     int bn_fused;           // LEDN_OPT_BN_FUSED: the persistent one-pass BatchNorm backward may be launched
     int dw_bwd_workgroups;  // LEDN_OPT_DW_BWD_WORKGROUPS: workgroups of the fused depthwise 3x3 backward (dwconv.hip)
+    int s2_dgrad;           // LEDN_OPT_S2_DGRAD: 3x3 stride-2 data gradients as parity sub-convolutions (conv_mfma.hip)
 };
 Options& options();
 // A/B measurement knobs (getenv) are honoured only in experimental mode (LEDN_EXPERIMENTAL=1): an old shell export must

@@ -267,6 +267,8 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, groups=1, xadd=None, in_scale=None, 
     d.KH, d.KW, d.stride, d.pad, d.dil, d.groups = KH, KW, stride, pad, dil, groups
     d.in_act, d.act_out, d.res_mode = in_act, act, res_mode if res is not None else RES_NONE
     d.dtype_x, d.dtype_y, d.transposed = _dt(x), _dt(y), int(transposed)
+    if _query == 's2_dgrad':
+        return int(lib.cdll.ledn_conv2d_s2_dgrad_applies(d))
     if _query:
         return int(lib.cdll.ledn_conv2d_uses_mfma(d))
     _run_stats(lib, 'ledn_conv2d', x, stats, defer_stats, d, work=_TIMING is not None and (
@@ -281,6 +283,13 @@ def conv2d_kernel_id(x, w, **kw):
     2 conv1x1_mfma_kernel, 3 conv3x3_reg_kernel, 4 conv3x3_narrowin_mfma_kernel, 5 conv_f32_mfma_kernel, 6 head_fwd_kernel,
     7 head_mc_fwd_kernel, 8 head_mc_dgrad_kernel (the heads with 3 .. 32 classes, csrc/head_mc.hip)"""
     return conv2d(x, w, _query=True, **kw)
+
+
+def conv2d_s2_dgrad_applies(x, w, **kw):
+    """True if conv2d(x, w, transposed=True, **kw) runs on conv_s2dgrad_mfma_kernel, the parity form of the 3x3 stride-2
+    data gradient (ledn_conv2d_s2_dgrad_applies, LEDN_OPT_S2_DGRAD); no launch"""
+    kw.setdefault('transposed', True)
+    return bool(conv2d(x, w, _query='s2_dgrad', **kw))
 
 
 def im2col_stem(x):

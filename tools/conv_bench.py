@@ -1,6 +1,7 @@
 """Micro-benchmark of the conv entries on the shapes of the bs16 1024x1024 train step.
 
     python tools/conv_bench.py [--iters 20]
+    python tools/conv_bench.py --only dgrad --s2-dgrad 0,1     # the stride-2 data gradients, both forms in one process
 
 Prints one line per shape: HIP-event time per launch, algorithmic GB/s (unique activation bytes
 in + out) and TFLOP/s.  GPU only (the product path has no CPU fallback).
@@ -29,7 +30,10 @@ SHAPES = [
     ('wgrad', 32, 32, 1, 1, 1, 16, 512, 512),
     ('fwd', 32, 32, 3, 2, 1, 16, 512, 512),
     ('dgrad', 32, 32, 3, 2, 1, 16, 512, 512),
+    ('dgradacc', 32, 32, 3, 2, 1, 16, 512, 512),     # the stem layer as the step runs it: bf16 addend (gradient fan-in)
     ('wgrad', 32, 32, 3, 2, 1, 16, 512, 512),
+    ('dgrad', 64, 128, 3, 2, 1, 16, 128, 128),
+    ('dgrad', 128, 256, 3, 2, 1, 16, 64, 64),
     ('fwd', 32, 2, 3, 1, 1, 16, 512, 512),
     ('fwdraw', 32, 2, 3, 1, 1, 16, 512, 512),        # no statistics, no prologue
     ('fwdpro', 32, 2, 3, 1, 1, 16, 512, 512),        # training: BatchNorm + ReLU prologue, bias, raw bf16 output, no statistics
@@ -63,6 +67,8 @@ def main():
     ap.add_argument('--only', default='', help='substring filter on the kind (fwd/dgrad/wgrad)')
     ap.add_argument('--k', type=int, default=0, help='only this kernel size')
     ap.add_argument('--ab', default='', help='comma list of LEDN_OPT_STREAM_FAST values to time each shape under')
+    ap.add_argument('--s2-dgrad', default='', help='comma list of LEDN_OPT_S2_DGRAD values (0 zero-upsampled form, 1 parity '
+                    'kernel) to time each dgrad row under, like --ab')
     args = ap.parse_args()
     from led_net_amd import _lib
     _lib.get_lib().set_option(0, args.conv_wgs)
@@ -101,14 +107,23 @@ def main():
             wp = ops.pack_conv_weights(w, 1, grp) if ops.mfma_weight_ok(w, grp) else None
             fn = lambda: ops.conv2d(dz, w, stride=s, pad=pad, groups=grp, transposed=True, out_hw=(H, W), w_bf16=wp)
             nbytes = x.numel() * 2 + dz.numel() * 2
+        elif kind == 'dgradacc':
+            wp = ops.pack_conv_weights(w, 1, grp)
+            fn = lambda: ops.conv2d(dz, w, stride=s, pad=pad, groups=grp, transposed=True, out_hw=(H, W), w_bf16=wp,
+                                    res=x, res_mode=ops.RES_ADD)
+            nbytes = 2 * x.numel() * 2 + dz.numel() * 2
         else:
             fn = lambda: ops.conv2d_wgrad(x, dz, tuple(w.shape), stride=s, pad=pad, groups=grp)
             nbytes = x.numel() * 2 + dz.numel() * 2
         flops = 2.0 * N * Ho * Wo * co * (ci // grp) * k * k
-        line = f'{kind:5s} {k}x{k} {ci:3d}->{co:3d} g{grp} s{s} {N}x{H}x{W}:'
-        for opt in ([int(v) for v in args.ab.split(',')] if args.ab else [None]):
+        line = f'{kind:8s} {k}x{k} {ci:3d}->{co:3d} g{grp} s{s} {N}x{H}x{W}:'
+        if args.s2_dgrad and kind.startswith('dgrad'):
+            variants = [(_lib.OPT_S2_DGRAD, int(v)) for v in args.s2_dgrad.split(',')]
+        else:
+            variants = [(_lib.OPT_STREAM_FAST, int(v)) for v in args.ab.split(',')] if args.ab else [(None, None)]
+        for which, opt in variants:
             if opt is not None:
-                _lib.get_lib().set_option(2, opt)
+                _lib.get_lib().set_option(which, opt)
             for _ in range(3):
                 fn()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -121,6 +136,8 @@ def main():
             us = e0.elapsed_time(e1) * 1e3 / args.iters
             line += (f' [{opt}]' if opt is not None else '') + (f'{us:8.1f} us  {nbytes / us * 1e-3:7.0f} GB/s  '
                                                                   f'{flops / us * 1e-6:6.1f} TFLOP/s')
+        if args.s2_dgrad:
+            _lib.get_lib().set_option(_lib.OPT_S2_DGRAD, 1)
         print(line, flush=True)
 
 
