@@ -1191,8 +1191,8 @@ int ledn_sgd_step(const ledn_sgd_entry* table_dev, int n_tensors, long long max_
  *       coef       = min(1, max_norm / (total_norm + 1e-6))
  *       g' = (grad_scale*coef)*g + wd*p;  m = momentum*m + g';  p -= lr*m;  g = 0
  *     and norm_out (two device floats, may be NULL) receives {total_norm, coef}.  coef == 1 gives the bits of
- *     ledn_sgd_step.  A non-finite norm is not masked: coef is NaN and so are the updated parameters.  clip_value is
- *     ignored.  (total_norm is the norm of the gradient the update uses: with grad_scale = 1/world_size, DDP's mean.)
+ *     ledn_sgd_step.  A non-finite norm is not masked: coef is NaN and so are the updated parameters (a step that
+ *     is to be left out instead goes through ledn_optim_step_guarded, below).  clip_value is ignored.  (total_norm is the norm of the gradient the update uses: with grad_scale = 1/world_size, DDP's mean.)
  *   norm_type = LEDN_NORM_NONE: clip by value, g' = clamp(grad_scale*g, -clip_value, clip_value) + wd*p (NaN passes, as
  *     torch.clamp); partials, n_partials, max_norm and norm_out are ignored, no norm pass is needed.
  * LEDN_EINVAL: n_partials outside 1..LEDN_CLIP_MAX_PARTIALS, an unknown norm_type, max_norm <= 0 (norm modes),
@@ -1287,6 +1287,59 @@ int ledn_optim_step_ema(const ledn_optim_entry* table_dev, float* const* avg_tab
                         const ledn_optim_desc* d, float w, const float* w_dev, void* stream);
 int ledn_ema_update(const ledn_ema_entry* table_dev, int n_tensors, long long max_n, float w, const float* w_dev,
                     void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Step guard: an optimizer step whose gradient holds an Inf or a NaN is skipped, decided on the device (what mmengine's
+ * AmpOptimWrapper / torch.cuda.amp.GradScaler.step do for optimizer.step()).  Three calls on one stream, in this order,
+ * no host synchronisation; each launch boundary is the only hand-off between them:
+ *
+ * ledn_grad_finite_pass: reads the gradient of every tensor of the optimizer table (grid = (chunks, tensors),
+ *   chunks = min(LEDN_GUARD_MAX_CHUNKS, ceil(max_n / 4096))).  An element is bad when its exponent bits are all ones,
+ *   (bits & 0x7f800000) == 0x7f800000: +-Inf and every NaN; FLT_MAX, denormals and -0.0 are finite.  16-byte loads over
+ *   the 16-byte aligned part of a gradient, 4-byte loads for the 0-3 floats in front of and behind it.  Writes
+ *   bad[i] = 1 / 0 per tensor (cleared on the stream first; every workgroup that finds a bad element stores the same 1)
+ *   and one 0 / 1 word per workgroup, flags[tensor * chunks + chunk].  No atomics.
+ * ledn_step_guard_verdict: ONE workgroup.  ORs the flags and updates the persistent words:
+ *     a bad gradient:  skip = 1, skipped += 1, last_bad[] = bad[], last_iter = the iteration stamp, has_last = 1
+ *     otherwise:       skip = 0, applied += 1
+ *   bc1 = 1 - beta1^t and sqrt_bc2 = sqrt(1 - beta2^t), formed in double, t = the applied steps before this one + 1
+ *   (torch.optim.AdamW's step count when the scaler left steps out); grad_finite = 1 / 0 and skipped_steps = skipped as
+ *   floats (what a training loop logs).  The stamp is *iter_dev when iter_dev != NULL (a captured graph replays with a
+ *   new value), else iter.
+ * ledn_optim_step_guarded: ledn_optim_step (avg_table_dev == NULL) or ledn_optim_step_ema on the same arguments, with
+ *   AdamW's bias corrections read from the guard words (the descriptor's bc1 / sqrt_bc2 and sched_dev[2..3] are not
+ *   used).  skip == 0: the bits of ledn_optim_step(_ema) called with that t.  skip == 1: p, m and v keep their bits (no
+ *   weight decay either), g is zeroed, avg still moves towards the unchanged p with this call's w, and norm_out is
+ *   written as in an applied step.  It reads the guard words and writes none of them.
+ *   A gradient whose elements are all finite but whose norm overflows is NOT a skip: the clip coefficient comes out 0,
+ *   as under torch.
+ * LEDN_EINVAL, with nothing launched: a NULL guard or a NULL pointer in it, a NULL table, n_tensors / max_n <= 0, beta1 /
+ * beta2 outside [0, 1) (verdict), and for the guarded step whatever ledn_optim_step / ledn_optim_step_ema reject.
+ * The caller owns every buffer; words starts zeroed (or holds the counts of a resumed run). */
+#define LEDN_GUARD_MAX_CHUNKS 8
+typedef struct {            /* device memory, 8-byte aligned */
+    long long applied;      /* optimizer steps applied */
+    long long skipped;      /* ... and skipped */
+    int skip;               /* this step's verdict */
+    float bc1, sqrt_bc2;    /* AdamW's bias corrections for this step */
+    float grad_finite;      /* 1.0 / 0.0 */
+    float skipped_steps;    /* (float)skipped */
+    int has_last;           /* a step has been skipped: last_iter / last_bad are valid */
+    long long last_iter;    /* the stamp of the last skipped step */
+} ledn_guard_words;
+typedef struct {            /* host memory: the device buffers of one guard */
+    ledn_guard_words* words;
+    int* bad;               /* [n_tensors] this step */
+    int* flags;             /* [n_tensors * LEDN_GUARD_MAX_CHUNKS] per workgroup of the finite pass */
+    int* last_bad;          /* [n_tensors] bad[] of the last skipped step */
+} ledn_step_guard;
+int ledn_grad_finite_pass(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* guard,
+                          void* stream);
+int ledn_step_guard_verdict(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* guard,
+                            double beta1, double beta2, long long iter, const long long* iter_dev, void* stream);
+int ledn_optim_step_guarded(const ledn_optim_entry* table_dev, float* const* avg_table_dev, int n_tensors, long long max_n,
+                            const ledn_optim_desc* d, const ledn_step_guard* guard, float w, const float* w_dev,
+                            void* stream);
 
 #ifdef __cplusplus
 }

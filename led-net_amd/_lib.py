@@ -190,6 +190,14 @@ class OptimDesc(C.Structure):           # mirrors ledn_optim_desc
                 ('clip_value', C.c_float), ('norm_out', fp)]
 
 
+GUARD_MAX_CHUNKS = 8                    # include/ledn.h LEDN_GUARD_MAX_CHUNKS
+GUARD_WORDS = 12                        # sizeof(ledn_guard_words) / 4
+
+
+class StepGuardDesc(C.Structure):       # mirrors ledn_step_guard (device pointers)
+    _fields_ = [('words', vp), ('bad', vp), ('flags', vp), ('last_bad', vp)]
+
+
 _PROTOS = {
     'ledn_bn_act_bwd_reduce': ([C.POINTER(BnBwdDesc), vp], i32),
     'ledn_bn_act_bwd_apply': ([C.POINTER(BnBwdDesc), vp], i32),
@@ -270,6 +278,9 @@ _PROTOS = {
     'ledn_optim_step': ([vp, i32, i64, C.POINTER(OptimDesc), vp], i32),
     'ledn_optim_step_ema': ([vp, vp, i32, i64, C.POINTER(OptimDesc), C.c_float, fp, vp], i32),
     'ledn_ema_update': ([vp, i32, i64, C.c_float, fp, vp], i32),
+    'ledn_grad_finite_pass': ([vp, i32, i64, C.POINTER(StepGuardDesc), vp], i32),
+    'ledn_step_guard_verdict': ([vp, i32, i64, C.POINTER(StepGuardDesc), C.c_double, C.c_double, i64, vp, vp], i32),
+    'ledn_optim_step_guarded': ([vp, vp, i32, i64, C.POINTER(OptimDesc), C.POINTER(StepGuardDesc), C.c_float, fp, vp], i32),
     'ledn_abi_version': ([], i32),
     'ledn_set_workspace': ([vp, i64], i32),
     'ledn_bind_workspace': ([vp, vp, i64], i32),

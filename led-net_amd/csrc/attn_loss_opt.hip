@@ -1338,14 +1338,16 @@ __global__ void __launch_bounds__(256) optim_ema_kernel(const OptimArgs a, float
 // (every table entry of an AdamW step needs a second-moment pointer; the table lives on the device, so the caller says
 // whether it filled them in: ledn_optim_desc.has_v)
 // avgs == NULL: ledn_optim_step (optim_kernel); else ledn_optim_step_ema (optim_ema_kernel, same grid)
-static int optim_launch(const ledn_optim_entry* table_dev, float* const* avgs, int n_tensors, long long max_n,
-                        const ledn_optim_desc* d, float ema_w, const float* ema_w_dev, hipStream_t s) {
+// the checks of an optimizer descriptor and its kernel arguments; *clip_out: the OPT_CLIP_* instance.  dev_bc: the bias
+// corrections come from device memory (ledn_optim_step_guarded), the descriptor's are not looked at
+static int optim_prepare(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_optim_desc* d,
+                         bool dev_bc, OptimArgs* out, int* clip_out) {
     LEDN_REQUIRE(table_dev && d && n_tensors > 0 && max_n > 0);
     LEDN_REQUIRE(d->kind == LEDN_OPTIM_SGD || d->kind == LEDN_OPTIM_ADAMW);
     if (d->kind == LEDN_OPTIM_ADAMW) {
         LEDN_REQUIRE(d->has_v);
         LEDN_REQUIRE(d->beta1 >= 0.0 && d->beta1 < 1.0 && d->beta2 >= 0.0 && d->beta2 < 1.0 && d->eps > 0.f);
-        LEDN_REQUIRE(d->sched_dev || (d->bc1 > 0.f && d->sqrt_bc2 > 0.f));
+        LEDN_REQUIRE(dev_bc || d->sched_dev || (d->bc1 > 0.f && d->sqrt_bc2 > 0.f));
     }
     int clip = OPT_CLIP_OFF;
     if (d->clip == LEDN_CLIP_NORM) {
@@ -1370,9 +1372,24 @@ static int optim_launch(const ledn_optim_entry* table_dev, float* const* avgs, i
     a.partials = d->partials, a.n_partials = d->n_partials;
     a.max_norm = d->max_norm, a.clip_value = d->clip_value;
     a.norm_out = d->norm_out;
-    long chunks = cdiv(max_n, 256 * 8);
-    if (chunks > 64) chunks = 64;
-    const dim3 grid((unsigned)chunks, (unsigned)n_tensors);
+    *out = a;
+    *clip_out = clip;
+    return LEDN_OK;
+}
+
+// grid.x of the optimizer launches
+static long optim_chunks(long long max_n) {
+    const long chunks = cdiv(max_n, 256 * 8);
+    return chunks > 64 ? 64 : chunks;
+}
+
+static int optim_launch(const ledn_optim_entry* table_dev, float* const* avgs, int n_tensors, long long max_n,
+                        const ledn_optim_desc* d, float ema_w, const float* ema_w_dev, hipStream_t s) {
+    OptimArgs a;
+    int clip;
+    const int rc = optim_prepare(table_dev, n_tensors, max_n, d, false, &a, &clip);
+    if (rc != LEDN_OK) return rc;
+    const dim3 grid((unsigned)optim_chunks(max_n), (unsigned)n_tensors);
 #define LEDN_OPTIM(KIND, CLIP)                                                                                  \
     do {                                                                                                        \
         if (avgs) LEDN_LAUNCH((optim_ema_kernel<KIND, CLIP>), grid, dim3(256), 0, s, a, avgs, ema_w, ema_w_dev); \
@@ -1453,6 +1470,302 @@ int ema_update_impl(const ledn_ema_entry* table_dev, int n_tensors, long long ma
     long chunks = cdiv(max_n, 256 * 8);
     if (chunks > 64) chunks = 64;
     LEDN_LAUNCH(ema_update_kernel, dim3((unsigned)chunks, (unsigned)n_tensors), dim3(256), 0, s, table_dev, w, w_dev);
+    return check_launch();
+}
+
+// ===========================================================================
+// step guard (ledn_grad_finite_pass, ledn_step_guard_verdict, ledn_optim_step_guarded): an optimizer step whose gradient
+// holds an Inf or a NaN leaves parameters and optimizer state alone.  Three launches in stream order; the launch boundary
+// is the only hand-off: the finite pass writes bad[] and one flag per workgroup, the one-workgroup verdict turns them into
+// the persistent words {skip, counts, bias corrections, log mirrors, sticky record}, and the optimizer launch only READS
+// those words -- no workgroup of it reads anything another workgroup of the same launch writes, so there is no ticket,
+// no spin and no atomic anywhere.
+// ===========================================================================
+__device__ __forceinline__ unsigned nonfinite_bits(unsigned u) { return (u & 0x7f800000u) == 0x7f800000u ? 1u : 0u; }
+__device__ __forceinline__ unsigned nonfinite4(const uint4& v) {
+    return nonfinite_bits(v.x) | nonfinite_bits(v.y) | nonfinite_bits(v.z) | nonfinite_bits(v.w);
+}
+
+// grid = (chunks, tensors) with few, long chunks (guard_chunks): most tensors of a network are small, every workgroup
+// costs a table read, a barrier pair and a flag store whether it has elements or not, and the verdict reads every flag
+// (the optimizer launch's 64 chunks per tensor would be 25472 workgroups and flag words for the shipped model).
+// Per tensor: head = the 0-3 floats in front of the first 16-byte aligned address, then nvec 16-byte vectors (grid-stride over the chunks, four loads in flight per trip), then 0-3 tail
+// floats; head and tail go to the first threads of chunk 0.  Every workgroup stores its own flag word; the ones that saw a
+// bad element also store the same 1 to bad[tensor] (cleared by the memset node in front of the launch).
+__global__ void __launch_bounds__(256) grad_finite_kernel(const ledn_optim_entry* table, int* bad, int* flags) {
+    __shared__ int s_bad;
+    const ledn_optim_entry e = table[blockIdx.y];
+    const int t = threadIdx.x;
+    const unsigned* g = reinterpret_cast<const unsigned*>(e.g);
+    long head = (long)((16u - ((uintptr_t)g & 15u)) & 15u) >> 2;
+    if (head > e.n) head = e.n;
+    const long nvec = (e.n - head) >> 2;
+    const int tail = (int)(e.n - head - (nvec << 2));
+    const uint4* gv = reinterpret_cast<const uint4*>(g + head);
+    const long stride = (long)gridDim.x * 256;
+    unsigned acc = 0u;
+    long v = (long)blockIdx.x * 256 + t;
+    for (; v + 3 * stride < nvec; v += 4 * stride) {
+        const uint4 a = gv[v], b = gv[v + stride], c = gv[v + 2 * stride], d = gv[v + 3 * stride];
+        acc |= nonfinite4(a) | nonfinite4(b) | nonfinite4(c) | nonfinite4(d);
+    }
+    for (; v < nvec; v += stride) acc |= nonfinite4(gv[v]);
+    if (blockIdx.x == 0) {
+        if (t < head) acc |= nonfinite_bits(g[t]);
+        if (t < tail) acc |= nonfinite_bits(g[head + (nvec << 2) + t]);
+    }
+    if (t == 0) s_bad = 0;
+    __syncthreads();
+    if (acc) s_bad = 1;                                     // (every writer stores the same value)
+    __syncthreads();
+    if (t == 0) {
+        const int b = s_bad;
+        flags[(long)blockIdx.y * gridDim.x + blockIdx.x] = b;
+        if (b) bad[blockIdx.y] = 1;
+    }
+}
+
+// grid.x of the finite pass = flag words per tensor: 4096 floats (four 16-byte loads per thread) per trip
+static long guard_chunks(long long max_n) {
+    const long chunks = cdiv(max_n, 4096);
+    return chunks > LEDN_GUARD_MAX_CHUNKS ? LEDN_GUARD_MAX_CHUNKS : chunks;
+}
+
+static int guard_check(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* gd) {
+    LEDN_REQUIRE(table_dev && n_tensors > 0 && max_n > 0);
+    LEDN_REQUIRE(gd && gd->words && gd->bad && gd->flags && gd->last_bad);
+    LEDN_REQUIRE(((uintptr_t)gd->words & 7u) == 0);
+    return LEDN_OK;
+}
+
+int grad_finite_pass_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* gd,
+                          hipStream_t s) {
+    const int rc = guard_check(table_dev, n_tensors, max_n, gd);
+    if (rc != LEDN_OK) return rc;
+    if (hipMemsetAsync(gd->bad, 0, sizeof(int) * (size_t)n_tensors, s) != hipSuccess) return LEDN_ELAUNCH;
+    LEDN_LAUNCH(grad_finite_kernel, dim3((unsigned)guard_chunks(max_n), (unsigned)n_tensors), dim3(256), 0, s, table_dev,
+                gd->bad, gd->flags);
+    return check_launch();
+}
+
+// one workgroup.  Thread 0 alone touches the words; the sticky copy of bad[] is spread over the threads.
+__global__ void __launch_bounds__(256) step_guard_verdict_kernel(ledn_guard_words* w, const int* bad, const int* flags,
+                                                                 int* last_bad, int n_tensors, long n_flags, double beta1,
+                                                                 double beta2, long long iter, const long long* iter_dev) {
+    __shared__ int s_bad;
+    const int t = threadIdx.x;
+    int acc = 0;
+    for (long i = t; i < n_flags; i += 256) acc |= flags[i];
+    if (t == 0) s_bad = 0;
+    __syncthreads();
+    if (acc) s_bad = 1;
+    __syncthreads();
+    const int skip = s_bad;
+    if (skip)
+        for (int i = t; i < n_tensors; i += 256) last_bad[i] = bad[i];
+    if (t == 0) {
+        const long long applied = w->applied, skipped = w->skipped + (skip ? 1 : 0);
+        const double tt = (double)(applied + 1);            // the step count an applied step has (torch: 1-based)
+        w->bc1 = (float)(1.0 - pow(beta1, tt));
+        w->sqrt_bc2 = (float)sqrt(1.0 - pow(beta2, tt));
+        w->skip = skip;
+        w->applied = applied + (skip ? 0 : 1);
+        w->skipped = skipped;
+        w->grad_finite = skip ? 0.f : 1.f;
+        w->skipped_steps = (float)skipped;
+        if (skip) {
+            w->has_last = 1;
+            w->last_iter = iter_dev ? *iter_dev : iter;
+        }
+    }
+}
+
+int step_guard_verdict_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* gd,
+                            double beta1, double beta2, long long iter, const long long* iter_dev, hipStream_t s) {
+    const int rc = guard_check(table_dev, n_tensors, max_n, gd);
+    if (rc != LEDN_OK) return rc;
+    LEDN_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
+    LEDN_REQUIRE(!iter_dev || ((uintptr_t)iter_dev & 7u) == 0);
+    LEDN_LAUNCH(step_guard_verdict_kernel, dim3(1), dim3(256), 0, s, gd->words, gd->bad, gd->flags, gd->last_bad, n_tensors,
+                guard_chunks(max_n) * (long)n_tensors, beta1, beta2, iter, iter_dev);
+    return check_launch();
+}
+
+// the averaged copy of a step that is left out: avg + w * (p - avg) with every operation rounded on its own, so that the
+// same f32 expression in torch gives its bits on the device too (ema_lerp's fused form is the applied step's)
+__device__ __forceinline__ float ema_lerp_skip(float w, float avg, float p) { return opt_add(avg, opt_mul(w, opt_add(p, -avg))); }
+
+// optim_ema_kernel with the skip predicate and the bias corrections of the guard words; EMA = false is optim_kernel's
+// column set (avgs == NULL).  A kernel of its own for the reason optim_ema_kernel is one: the existing launches keep
+// their code.  Everything between the skip branch and the end is optim_ema_kernel's text, so an applied step has its bits.
+template <int KIND, int CLIP, bool EMA>
+__global__ void __launch_bounds__(256) optim_guarded_kernel(const OptimArgs a, float* const* avgs, float w_arg, const float* w_dev,
+                                                            const ledn_guard_words* gw) {
+    const ledn_optim_entry e = a.table[blockIdx.y];
+    float* avg = nullptr;
+    float ema_w = 1.f;
+    if constexpr (EMA) {
+        avg = avgs[blockIdx.y];
+        ema_w = w_dev ? *w_dev : w_arg;
+    }
+    const bool vec = ((((uintptr_t)e.p | (uintptr_t)e.g | (uintptr_t)e.m | (uintptr_t)e.v | (uintptr_t)avg) & 15u) == 0) && e.n >= 4;
+    const bool ema_copy = ema_w >= 1.f;                    // (the same in every thread of the grid)
+    // (whole workgroup: nothing of this tensor is its to update; chunk 0 always stays, it owns the tail)
+    if ((long)blockIdx.x * blockDim.x * (vec ? 4 : 1) >= e.n) return;
+    const int t = threadIdx.x;
+    const int skip = gw->skip;                             // (one word, the same in every workgroup: the verdict launch wrote it)
+    float A = a.A, B = a.B, bc1 = 1.f, sbc2 = 1.f;
+    if (a.sched_dev) {
+        A = a.sched_dev[0];
+        B = a.sched_dev[1];
+    }
+    if constexpr (KIND == LEDN_OPTIM_ADAMW) {
+        bc1 = gw->bc1;
+        sbc2 = gw->sqrt_bc2;
+    }
+    OptimConsts c;
+    c.gs = a.gscale;
+    if constexpr (CLIP == OPT_CLIP_L2 || CLIP == OPT_CLIP_INF) {
+        __shared__ float s_w[4];
+        float tot = block256_combine<CLIP == OPT_CLIP_INF>(t < a.n_partials ? a.partials[t] : 0.f, s_w);
+        if constexpr (CLIP == OPT_CLIP_L2) tot = sqrtf(tot);
+        tot *= a.gscale;                                   // the norm of the gradient the update uses (DDP's mean)
+        const float q = a.max_norm / (tot + 1e-6f);
+        const float coef = q > 1.f ? 1.f : q;              // torch.clamp(max=1): a NaN coefficient stays NaN
+        if (a.norm_out && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {
+            a.norm_out[0] = tot;
+            a.norm_out[1] = coef;
+        }
+        c.gs = a.gscale * coef;
+    }
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long i0 = (long)blockIdx.x * blockDim.x + t;
+    if (skip) {
+        // the step is left out: only the gradient is cleared and the averaged copy follows the unchanged p
+        if (vec) {
+            const long nvec = e.n >> 2;
+            float4* gv = reinterpret_cast<float4*>(e.g);
+            for (long i = i0; i < nvec; i += stride) {
+                gv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (EMA) {
+                    float4* av = reinterpret_cast<float4*>(avg);
+                    const float4 p = reinterpret_cast<const float4*>(e.p)[i];
+                    float4 x = p;
+                    if (!ema_copy) {
+                        x = av[i];
+                        x.x = ema_lerp_skip(ema_w, x.x, p.x);
+                        x.y = ema_lerp_skip(ema_w, x.y, p.y);
+                        x.z = ema_lerp_skip(ema_w, x.z, p.z);
+                        x.w = ema_lerp_skip(ema_w, x.w, p.w);
+                    }
+                    av[i] = x;
+                }
+            }
+            const long i = (nvec << 2) + t;
+            if (blockIdx.x == 0 && i < e.n) {
+                e.g[i] = 0.f;
+                if constexpr (EMA) avg[i] = ema_copy ? e.p[i] : ema_lerp_skip(ema_w, avg[i], e.p[i]);
+            }
+        } else {
+            for (long i = i0; i < e.n; i += stride) {
+                e.g[i] = 0.f;
+                if constexpr (EMA) avg[i] = ema_copy ? e.p[i] : ema_lerp_skip(ema_w, avg[i], e.p[i]);
+            }
+        }
+        return;
+    }
+    c.cv = a.clip_value;
+    c.lr = e.lr_mult * A + B;
+    c.wd = e.wd_mult * a.weight_decay;
+    c.mom = a.momentum;
+    c.decay = 1.f - c.lr * c.wd;
+    c.b1 = a.b1, c.omb1 = a.omb1, c.b2 = a.b2, c.omb2 = a.omb2;
+    c.step = c.lr / bc1;
+    c.sbc2 = sbc2;
+    c.eps = a.eps;
+    if (vec) {
+        const long nvec = e.n >> 2;
+        float4* pv = reinterpret_cast<float4*>(e.p);
+        float4* gv = reinterpret_cast<float4*>(e.g);
+        float4* mv = reinterpret_cast<float4*>(e.m);
+        float4* vv = reinterpret_cast<float4*>(e.v);
+        for (long i = i0; i < nvec; i += stride) {
+            float4 p = pv[i], m = mv[i], v = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 g = gv[i];
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = vv[i];
+            optim_update<KIND, CLIP>(c, p.x, g.x, m.x, v.x);
+            optim_update<KIND, CLIP>(c, p.y, g.y, m.y, v.y);
+            optim_update<KIND, CLIP>(c, p.z, g.z, m.z, v.z);
+            optim_update<KIND, CLIP>(c, p.w, g.w, m.w, v.w);
+            mv[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) vv[i] = v;
+            pv[i] = p;
+            gv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (EMA) {
+                float4* av = reinterpret_cast<float4*>(avg);
+                float4 x = p;
+                if (!ema_copy) {
+                    x = av[i];
+                    x.x = ema_lerp(ema_w, x.x, p.x);
+                    x.y = ema_lerp(ema_w, x.y, p.y);
+                    x.z = ema_lerp(ema_w, x.z, p.z);
+                    x.w = ema_lerp(ema_w, x.w, p.w);
+                }
+                av[i] = x;
+            }
+        }
+        const long done = nvec << 2;
+        if (blockIdx.x == 0 && done + t < e.n) {
+            const long i = done + t;
+            float p = e.p[i], m = e.m[i], v = 0.f;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = e.v[i];
+            optim_update<KIND, CLIP>(c, p, e.g[i], m, v);
+            e.m[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) e.v[i] = v;
+            e.p[i] = p;
+            e.g[i] = 0.f;
+            if constexpr (EMA) avg[i] = ema_copy ? p : ema_lerp(ema_w, avg[i], p);
+        }
+    } else {
+        for (long i = i0; i < e.n; i += stride) {
+            float p = e.p[i], m = e.m[i], v = 0.f;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) v = e.v[i];
+            optim_update<KIND, CLIP>(c, p, e.g[i], m, v);
+            e.m[i] = m;
+            if constexpr (KIND == LEDN_OPTIM_ADAMW) e.v[i] = v;
+            e.p[i] = p;
+            e.g[i] = 0.f;
+            if constexpr (EMA) avg[i] = ema_copy ? p : ema_lerp(ema_w, avg[i], p);
+        }
+    }
+}
+
+int optim_step_guarded_impl(const ledn_optim_entry* table_dev, float* const* avgs, int n_tensors, long long max_n,
+                            const ledn_optim_desc* d, const ledn_step_guard* gd, float w, const float* w_dev, hipStream_t s) {
+    OptimArgs a;
+    int clip;
+    int rc = optim_prepare(table_dev, n_tensors, max_n, d, true, &a, &clip);
+    if (rc != LEDN_OK) return rc;
+    rc = guard_check(table_dev, n_tensors, max_n, gd);
+    if (rc != LEDN_OK) return rc;
+    LEDN_REQUIRE(!avgs || w_dev || (w > 0.f && w <= 1.f));
+    const dim3 grid((unsigned)optim_chunks(max_n), (unsigned)n_tensors);
+    const ledn_guard_words* gw = gd->words;
+#define LEDN_OPTIM(KIND, CLIP)                                                                                              \
+    do {                                                                                                                    \
+        if (avgs) LEDN_LAUNCH((optim_guarded_kernel<KIND, CLIP, true>), grid, dim3(256), 0, s, a, avgs, w, w_dev, gw);     \
+        else LEDN_LAUNCH((optim_guarded_kernel<KIND, CLIP, false>), grid, dim3(256), 0, s, a, avgs, w, w_dev, gw);         \
+    } while (0)
+#define LEDN_OPTIM_KIND(KIND)                                        \
+    switch (clip) {                                                  \
+        case OPT_CLIP_L2: LEDN_OPTIM(KIND, OPT_CLIP_L2); break;      \
+        case OPT_CLIP_INF: LEDN_OPTIM(KIND, OPT_CLIP_INF); break;    \
+        case OPT_CLIP_VALUE: LEDN_OPTIM(KIND, OPT_CLIP_VALUE); break;\
+        default: LEDN_OPTIM(KIND, OPT_CLIP_OFF); break;              \
+    }
+    if (d->kind == LEDN_OPTIM_SGD) { LEDN_OPTIM_KIND(LEDN_OPTIM_SGD) } else { LEDN_OPTIM_KIND(LEDN_OPTIM_ADAMW) }
+#undef LEDN_OPTIM_KIND
+#undef LEDN_OPTIM
     return check_launch();
 }
 

@@ -174,6 +174,12 @@ int optim_step_impl(const ledn_optim_entry* table_dev, int n_tensors, long long 
 int optim_step_ema_impl(const ledn_optim_entry* table_dev, float* const* avg_table_dev, int n_tensors, long long max_n,
                         const ledn_optim_desc* d, float w, const float* w_dev, hipStream_t s);
 int ema_update_impl(const ledn_ema_entry* table_dev, int n_tensors, long long max_n, float w, const float* w_dev, hipStream_t s);
+int grad_finite_pass_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* gd,
+                          hipStream_t s);
+int step_guard_verdict_impl(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* gd,
+                            double beta1, double beta2, long long iter, const long long* iter_dev, hipStream_t s);
+int optim_step_guarded_impl(const ledn_optim_entry* table_dev, float* const* avgs, int n_tensors, long long max_n,
+                            const ledn_optim_desc* d, const ledn_step_guard* gd, float w, const float* w_dev, hipStream_t s);
 }  // namespace ledn
 
 #include <mutex>
@@ -833,6 +839,19 @@ int ledn_optim_step_ema(const ledn_optim_entry* table_dev, float* const* avg_tab
 int ledn_ema_update(const ledn_ema_entry* table_dev, int n_tensors, long long max_n, float w, const float* w_dev,
                     void* stream) {
     return ema_update_impl(table_dev, n_tensors, max_n, w, w_dev, S(stream));
+}
+int ledn_grad_finite_pass(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* guard,
+                          void* stream) {
+    return grad_finite_pass_impl(table_dev, n_tensors, max_n, guard, S(stream));
+}
+int ledn_step_guard_verdict(const ledn_optim_entry* table_dev, int n_tensors, long long max_n, const ledn_step_guard* guard,
+                            double beta1, double beta2, long long iter, const long long* iter_dev, void* stream) {
+    return step_guard_verdict_impl(table_dev, n_tensors, max_n, guard, beta1, beta2, iter, iter_dev, S(stream));
+}
+int ledn_optim_step_guarded(const ledn_optim_entry* table_dev, float* const* avg_table_dev, int n_tensors, long long max_n,
+                            const ledn_optim_desc* d, const ledn_step_guard* guard, float w, const float* w_dev,
+                            void* stream) {
+    return optim_step_guarded_impl(table_dev, avg_table_dev, n_tensors, max_n, d, guard, w, w_dev, S(stream));
 }
 
 }  // extern "C"

@@ -1362,11 +1362,14 @@ class OptimTable:
             self.avg_table = torch.tensor([a.data_ptr() for a in avgs], dtype=torch.int64).to(params[0].device)
 
     def step(self, kind, lr_a, lr_b=0.0, *, momentum=0.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0,
-             t=1, sched_dev=None, clip=None, ema_w=None, ema_dev=None):
+             t=1, sched_dev=None, clip=None, ema_w=None, ema_dev=None, guard=None):
         """one launch.  kind: _lib.OPTIM_SGD / OPTIM_ADAMW; tensor i moves at lr_mults[i] * lr_a + lr_b with the decay
         wd_mults[i] * weight_decay; t: AdamW's 1-based step count; sched_dev: None or the four device floats
         optim_scalars() describes (they then replace lr_a, lr_b and t); clip: as SgdTable.step.  A table with avgs
-        needs the averaging weight, ema_w (0 < w <= 1; 1 copies) or ema_dev (one device float, which wins)."""
+        needs the averaging weight, ema_w (0 < w <= 1; 1 copies) or ema_dev (one device float, which wins).
+        guard: None or a StepGuard whose finite pass and verdict have been queued on this stream for this table; the
+        launch is then ledn_optim_step_guarded, which leaves a step with a non-finite gradient out and takes AdamW's bias
+        corrections from the guard's count of applied steps (t is not used)."""
         lib = _lib.get_lib()
         d = _lib.OptimDesc()
         d.kind, d.has_v = int(kind), int(self.has_v)
@@ -1390,6 +1393,15 @@ class OptimTable:
         work = _ops._TIMING is not None and (f'optim {self.n} tensors', (32 if self.has_v else 16) * nel, 0, 'optim_kernel')
         if (self.avgs is None) != (ema_w is None and ema_dev is None):
             raise LednError('OptimTable.step: ema_w / ema_dev go with a table built with avgs, and such a table needs one')
+        if guard is not None:
+            guard.check(self)
+            _check_ema_w(lib, ema_dev)
+            gd = guard.desc()
+            _run(lib, 'ledn_optim_step_guarded', self.ref, self.table.data_ptr(), _p(self.avg_table), self.n, self.max_n,
+                 C.byref(d), C.byref(gd), float(ema_w if ema_w is not None else 0.0), _p(ema_dev),
+                 work=work and (work[0] + ' guarded', work[1] + (8 * nel if self.avgs is not None else 0), 0,
+                                'optim_guarded_kernel'))
+            return
         if self.avgs is None:
             _run(lib, 'ledn_optim_step', self.ref, self.table.data_ptr(), self.n, self.max_n, C.byref(d), work=work)
             return
@@ -1404,6 +1416,86 @@ def _check_ema_w(lib, ema_dev):
         if ema_dev.dtype != torch.float32 or ema_dev.numel() != 1:
             raise LednError('ema_dev: one float32 value')
         _check(lib, ema_dev)
+
+
+class StepGuard:
+    """Device state of the step guard for OptimTable.step(guard=): ONE persistent int32 buffer
+    [ledn_guard_words | bad[n] | last_bad[n] | flags[8 n]] (its own allocation, like GradClip's).  Per step, on one
+    stream and in this order: finite_pass(table), verdict(table, ...), table.step(..., guard=self).
+    grad_finite / skipped_steps: 0-dim float32 views, current after every step and every graph replay."""
+
+    def __init__(self, device, n_tensors):
+        n, w = int(n_tensors), _lib.GUARD_WORDS
+        if n <= 0:
+            raise LednError('StepGuard: n_tensors > 0')
+        self.n = n
+        self.buf = torch.zeros(w + n * (2 + _lib.GUARD_MAX_CHUNKS), dtype=torch.int32, device=device)
+        self.words = self.buf[:w]
+        self.bad, self.last_bad, self.flags = self.buf[w:w + n], self.buf[w + n:w + 2 * n], self.buf[w + 2 * n:]
+        self.counts = self.words[0:4].view(torch.int64)           # {applied, skipped}
+        self.skip = self.words[4]
+        self.bias_corrections = self.words[5:7].view(torch.float32)
+        mirrors = self.words[7:9].view(torch.float32)
+        mirrors[0] = 1.0
+        self.grad_finite, self.skipped_steps = mirrors[0], mirrors[1]
+        self.has_last = self.words[9]
+        self.last_iter = self.words[10:12].view(torch.int64)[0]
+
+    def check(self, table):
+        if table.n != self.n or table.ref.device != self.buf.device:
+            raise LednError('StepGuard: built for another optimizer table')
+        _check(_lib.get_lib(), self.buf)
+
+    def desc(self):
+        d = _lib.StepGuardDesc()
+        d.words, d.bad, d.flags, d.last_bad = _p(self.words), _p(self.bad), _p(self.flags), _p(self.last_bad)
+        return d
+
+    def finite_pass(self, table):
+        """bad[i] = tensor i's gradient holds an Inf or a NaN, and one flag per workgroup for the verdict"""
+        lib = _lib.get_lib()
+        self.check(table)
+        gd = self.desc()
+        nel = sum(p.numel() for p in table.keep[0])
+        _run(lib, 'ledn_grad_finite_pass', table.ref, table.table.data_ptr(), table.n, table.max_n, C.byref(gd),
+             work=_ops._TIMING is not None and (f'grad finite {table.n} tensors', 4 * nel, 0, 'grad_finite_kernel'))
+
+    def verdict(self, table, betas=(0.9, 0.999), it=0, iter_dev=None):
+        """the one-workgroup launch between the finite pass and the optimizer launch.  it: the iteration stamp kept
+        with a skipped step (iter_dev, one device int64, wins: a captured graph replays with a new value)"""
+        lib = _lib.get_lib()
+        self.check(table)
+        if iter_dev is not None:
+            if iter_dev.dtype != torch.int64 or iter_dev.numel() != 1:
+                raise LednError('iter_dev: one int64 value')
+            _check(lib, iter_dev)
+        gd = self.desc()
+        _run(lib, 'ledn_step_guard_verdict', table.ref, table.table.data_ptr(), table.n, table.max_n, C.byref(gd),
+             float(betas[0]), float(betas[1]), int(it), _p(iter_dev),
+             work=_ops._TIMING is not None and (f'step guard verdict {table.n} tensors',
+                                                4 * table.n * _lib.GUARD_MAX_CHUNKS, 0, 'step_guard_verdict_kernel'))
+
+    # host reads (each synchronises with the device)
+    def state(self):
+        """-> dict(applied=, skipped=): the counters a checkpoint keeps"""
+        a, k = self.counts.tolist()
+        return dict(applied=int(a), skipped=int(k))
+
+    def load_state(self, applied, skipped=0):
+        self.counts.copy_(torch.tensor([int(applied), int(skipped)], dtype=torch.int64))
+        self.words[8:9].view(torch.float32).fill_(float(int(skipped)))
+
+    def snapshot(self):
+        return self.buf.clone()
+
+    def restore(self, snap):
+        self.buf.copy_(snap)
+
+    def report(self):
+        """-> None, or (iteration stamp, indices of the tensors whose gradient was non-finite) of the last skipped step"""
+        if int(self.has_last) == 0:
+            return None
+        return int(self.last_iter), [i for i, b in enumerate(self.last_bad.tolist()) if b]
 
 
 class EmaTable:

@@ -1508,6 +1508,31 @@ def led_head_loss(h, inputs, batch_data_samples):
 # --------------------------------------------------------------------------- #
 # Trainer: SGD(momentum, wd) or AdamW + the config's scheduler list + data-parallel gradient all-reduce
 # --------------------------------------------------------------------------- #
+def parse_amp_wrapper(wrapper):
+    """mmengine ``optim_wrapper`` section -> True when it names AmpOptimWrapper (whose GradScaler leaves out the steps
+    with a non-finite gradient: the step guard), False for any other type.  AmpOptimWrapper's own keys are validated and
+    NOT applied: loss_scale ('dynamic', a positive number or a dict of GradScaler arguments) changes no bit here -- the
+    gradients are f32, bf16 activations have f32's exponent range and mmengine's scales are powers of two -- and dtype
+    may be None or 'bfloat16' (what the bf16 path computes in); 'float16' raises."""
+    if not isinstance(wrapper, dict) or wrapper.get('type') != 'AmpOptimWrapper':
+        return False
+    ls = wrapper.get('loss_scale', 512.0)
+    if isinstance(ls, str):
+        if ls != 'dynamic':
+            raise ValueError(f"optim_wrapper: loss_scale={ls!r} (expected 'dynamic', a positive number or a dict)")
+    elif isinstance(ls, dict):
+        unknown = sorted(set(ls) - {'init_scale', 'growth_factor', 'backoff_factor', 'growth_interval', 'enabled'})
+        if unknown:
+            raise ValueError(f'optim_wrapper: loss_scale has unknown GradScaler argument {unknown[0]!r}')
+    elif isinstance(ls, bool) or not isinstance(ls, (int, float)) or not (ls > 0 and math.isfinite(ls)):
+        raise ValueError(f'optim_wrapper: loss_scale={ls!r} must be a positive number')
+    dt = wrapper.get('dtype')
+    if dt not in (None, 'bfloat16', torch.bfloat16):
+        raise ValueError(f"optim_wrapper: dtype={dt!r} is not supported (None or 'bfloat16': activations are bf16 or f32, "
+                         f"gradients f32; there is no float16 path)")
+    return True
+
+
 def parse_clip_grad(clip_grad):
     """mmengine OptimWrapper's ``clip_grad`` -> None or ('norm', norm_type, max_norm) / ('value', clip_value):
     dict(max_norm=, norm_type=2) and dict(type='norm', ...) are torch.nn.utils.clip_grad_norm_'s arguments,
@@ -1559,7 +1584,7 @@ class Trainer:
 
     def __init__(self, model, cfg=None, world_size=1, lr=None, momentum=None, weight_decay=None,
                  max_iters=None, power=0.9, eta_min=0.0, bucket_mb=2.0, direct_grads=True, collectives=None,
-                 clip_grad=None, paramwise_cfg=None, ema=None):
+                 clip_grad=None, paramwise_cfg=None, ema=None, skip_nonfinite=None):
         # config: optim_wrapper = dict(type='OptimWrapper', optimizer=..., clip_grad=..., paramwise_cfg=...); a config
         # without that section keeps its optimizer at the top level.  (optim.py / DESIGN.md "Optimizer construction
         # from the config": every key is honoured or raises ValueError.)
@@ -1570,6 +1595,10 @@ class Trainer:
             clip_grad = wrapper.get('clip_grad')
         clip = parse_clip_grad(clip_grad)
         pw = O.parse_paramwise(paramwise_cfg if paramwise_cfg is not None else wrapper.get('paramwise_cfg'))
+        # the step guard (DESIGN.md "Skipping non-finite steps in the optimizer launch"): off unless the config's wrapper
+        # is an AmpOptimWrapper or the argument says so (the argument wins either way)
+        amp = parse_amp_wrapper(wrapper)
+        self.skip_nonfinite = amp if skip_nonfinite is None else bool(skip_nonfinite)
         self.model = model
         self.opt_kind = opt['kind']
         self.base_lr, self.wd = opt['lr'], opt['weight_decay']
@@ -1585,7 +1614,7 @@ class Trainer:
         # plain SGD under a lone PolyLR keeps the ledn_sgd_step(_clip) launch; everything else -- AdamW, per-parameter
         # multipliers, a scheduler list, weight averaging -- is ONE ledn_optim_step(_ema) launch over the extended table
         self._plain = self.opt_kind == 'SGD' and pw is None and self.sched.lone_poly
-        self._general = not self._plain or self.ema is not None
+        self._general = not self._plain or self.ema is not None or self.skip_nonfinite
         self.iter = 0
         self.world = world_size
         # gradient layout: [stem | everything else], each in module order.  The stem's backward comes LAST (and is
@@ -1636,6 +1665,7 @@ class Trainer:
         self.names = [n_ for n_, _ in late] + [n_ for n_, _ in early]
         self.mults = [mults.get(name, (1.0, 1.0)) for name in self.names]      # (lr_mult, decay_mult) per parameter
         self.table = None
+        self.guard, self._iter_dev, self._guard_resume = None, None, None     # (the guard is built with the table)
         # gradient clipping: the norm pass over flat_grad writes its per-workgroup partials into the trainer's own
         # persistent buffer [partials | total_norm | coef]; the SGD launch combines them in its prologue
         self._set_clip(clip)
@@ -1729,12 +1759,15 @@ class Trainer:
         pos = {id(p): i for i, p in enumerate(self.params)}
         live = {id(p) for p in getattr(self, 'live', [])} if self.table is not None else set()
         state = {}
+        # (torch.optim.AdamW's step counts the steps it APPLIED: with the step guard on, the guard's device counter)
+        counts = self._guard_counts() if self.skip_nonfinite else None
+        adam_step = counts['applied'] if counts is not None else self.iter
         for i, p in enumerate(order):
             if id(p) not in live:
                 continue
             k = pos[id(p)]
             if self.opt_kind == 'AdamW':
-                state[i] = {'step': torch.tensor(float(self.iter), dtype=torch.float32),
+                state[i] = {'step': torch.tensor(float(adam_step), dtype=torch.float32),
                             'exp_avg': self.moms[k].detach().clone().cpu(),
                             'exp_avg_sq': self.vs[k].detach().clone().cpu()}
             else:
@@ -1751,9 +1784,20 @@ class Trainer:
             g.update(initial_lr=self.base_lr * lr_mult, params=params)
             return g
         if self.paramwise is None:
-            return {'state': state, 'param_groups': [group(1.0, 1.0, list(range(len(order))))]}
-        return {'state': state, 'param_groups': [group(*(self.mults[pos[id(p)]] if id(p) in pos else (1.0, 1.0)), [i])
-                                                 for i, p in enumerate(order)]}
+            sd = {'state': state, 'param_groups': [group(1.0, 1.0, list(range(len(order))))]}
+        else:
+            sd = {'state': state, 'param_groups': [group(*(self.mults[pos[id(p)]] if id(p) in pos else (1.0, 1.0)), [i])
+                                                   for i, p in enumerate(order)]}
+        if self.skip_nonfinite:
+            sd['step_guard'] = counts                    # (a host read of the two device counters)
+        return sd
+
+    def _guard_counts(self):
+        if self.guard is not None:
+            return self.guard.state()
+        if self._guard_resume is not None:
+            return dict(applied=self._guard_resume[0], skipped=self._guard_resume[1])
+        return dict(applied=self.iter, skipped=0)
 
     def _group_lr(self, lr_mult):
         if lr_mult == 1.0:
@@ -1808,10 +1852,31 @@ class Trainer:
                     self.moms[k].copy_(buf.to(self.flat_mom.device, torch.float32).view_as(p))
         if step is not None:
             self.iter = step            # (AdamW's step count IS the iteration counter: mmengine steps both together)
+        if opt_sd.get('step_guard'):    # (... unless steps were left out: iterations = applied + skipped)
+            self.iter = int(opt_sd['step_guard'].get('applied', 0)) + int(opt_sd['step_guard'].get('skipped', 0))
         if schedulers:
             self.iter = int(schedulers[0].get('last_step', self.iter))
         if iter is not None:
             self.iter = int(iter)
+        if self.skip_nonfinite:
+            # AdamW's bias corrections follow the APPLIED steps; a checkpoint written without the guard applied every one
+            sg = opt_sd.get('step_guard') or {}
+            counts = (int(sg.get('applied', self.iter)), int(sg.get('skipped', 0)))
+            if self.guard is not None:
+                self.guard.load_state(*counts)
+            else:
+                self._guard_resume = counts
+
+    def nonfinite_report(self):
+        """the last skipped step, read from the device on demand (this synchronises): None when no step has been
+        skipped, else dict(iter=, params=[names of the parameters whose gradient held an Inf or a NaN])"""
+        if self.guard is None:
+            return None
+        rep = self.guard.report()
+        if rep is None:
+            return None
+        names = {id(p): n_ for n_, p in zip(self.names, self.params)}
+        return dict(iter=rep[0], params=[names[id(self.live[i])] for i in rep[1]])
 
     def lr(self):
         """the base group's learning rate at this iteration (optim.Schedule; a lone mmengine PolyLR by iteration:
@@ -1891,6 +1956,8 @@ class Trainer:
         averaging weight"""
         if self._ema_dev is not None:
             self._ema_dev.fill_(self._ema_w())
+        if self._iter_dev is not None:
+            self._iter_dev.fill_(self.iter)
         if self._lr_dev is None:
             return
         if not self._general:
@@ -2040,6 +2107,9 @@ class Trainer:
                     rest = [(a, p.detach()) for p, a in zip(self.params, self.emas) if p.grad is None]
                     rest += [(a, t.detach()) for _, t, a in self._ema_extra]
                     self._ema_table = T.EmaTable([a for a, _ in rest], [t for _, t in rest]) if rest else None
+                if self.skip_nonfinite:
+                    self.guard = T.StepGuard(self.flat_grad.device, self.table.n)
+                    self.guard.load_state(*(self._guard_resume or (self.iter, 0)))
             else:
                 self.table = T.SgdTable(self.live, self.live_views, [self.moms[i] for i in idx])
             if self.direct_grads:
@@ -2066,6 +2136,22 @@ class Trainer:
 
     def _train_step(self, inputs, data_samples, first):
         losses = self._forward_backward(inputs, data_samples, first)
+        return self._optimizer_step(losses)
+
+    def optimizer_step(self):
+        """the second half of train_step, for a caller that ran forward_backward and looked at (or changed) flat_grad:
+        gradient exchange, clip pass, step guard, the optimizer launch (which clears flat_grad), iteration count.
+        Returns the step's own entries of the result dict (grad_norm, grad_finite, skipped_steps: whichever are on).
+        (forward_backward starts no early exchange, so the whole buffer is exchanged here.)"""
+        assert self.table is not None, 'run one train_step first'
+        self._enter()
+        _Env.grad_ready = None
+        try:
+            return self._optimizer_step({})
+        finally:
+            self._leave()
+
+    def _optimizer_step(self, losses):
         if self.coll is not None:
             # what the backward did not already start: the stem's gradients (or everything)
             self._exchange(0, self.n_late if self._early_done else self.flat_grad.numel())
@@ -2074,6 +2160,11 @@ class Trainer:
         if (self._lr_dev is not None or self._ema_dev is not None) and not (
                 self.flat_grad.is_cuda and torch.cuda.is_current_stream_capturing()):
             self._refresh_dev()                 # eager step after a capture(): keep the device-resident rate current
+        if self.guard is not None:
+            # after the exchange, on the raw all-reduced buffer (before grad_scale, clipping and weight decay): the same
+            # verdict on every rank.  Three launches in line on the launch stream: finite pass, verdict, optimizer.
+            self.guard.finite_pass(self.table)
+            self.guard.verdict(self.table, self.betas, self.iter, iter_dev=self._iter_dev)
         if self.clip is not None:
             # after the exchange (and the wait for its stream): the norm of the all-reduced gradient, the same on every rank
             self.clip.norm_pass(self.flat_grad)
@@ -2081,7 +2172,8 @@ class Trainer:
             a, b, _, _ = self._optim_scalars()
             self.table.step(_lib.OPTIM_ADAMW if self.opt_kind == 'AdamW' else _lib.OPTIM_SGD, a, b, momentum=self.momentum,
                             betas=self.betas, eps=self.eps, weight_decay=self.wd, grad_scale=1.0 / self.world,
-                            t=self.iter + 1, sched_dev=self._lr_dev, clip=self.clip, ema_dev=self._ema_dev)
+                            t=self.iter + 1, sched_dev=self._lr_dev, clip=self.clip, ema_dev=self._ema_dev,
+                            guard=self.guard)
             if self._ema_table is not None:
                 self._ema_table.update(w_dev=self._ema_dev)
         elif self.clip is None:
@@ -2097,6 +2189,8 @@ class Trainer:
         if self.clip is not None and self.clip.norm_type != _lib.NORM_NONE:
             out['grad_norm'] = self.clip.total_norm     # (mmengine's log key; a view of the persistent buffer: a captured
             # graph's _static_out shows the value of each replay)
+        if self.guard is not None:
+            out['grad_finite'], out['skipped_steps'] = self.guard.grad_finite, self.guard.skipped_steps    # (views, likewise)
         return out
 
     # ------------------------------------------------------------------ #
@@ -2121,6 +2215,8 @@ class Trainer:
         self._static_samples = [SegDataSample(gt=self._static_lab[i], metainfo=dict(getattr(ds, 'metainfo', {}) or {}))
                                 for i, ds in enumerate(data_samples)]
         self._lr_dev = torch.zeros(4 if self._general else 1, dtype=torch.float32, device=dev)
+        if self.skip_nonfinite:
+            self._iter_dev = torch.zeros(1, dtype=torch.int64, device=dev)      # the stamp a skipped replay records
         self._valid_host = None         # (a second capture() starts from the new batch's padding extents)
         if inputs.dtype == torch.uint8 and getattr(self.model, 'pre_scale', None) is not None:
             # per-image valid extents (batch padding) live in a resident buffer the graph reads: replay() refreshes it
@@ -2131,7 +2227,8 @@ class Trainer:
             snap = ([p.detach().clone() for p in self.params], self.flat_mom.clone(),
                     [b.detach().clone() for b in self.model.buffers()], self.iter,
                     self.flat_v.clone() if self.flat_v is not None else None,
-                    self.flat_ema.clone() if self.flat_ema is not None else None, self.ema_steps)
+                    self.flat_ema.clone() if self.flat_ema is not None else None, self.ema_steps,
+                    self.guard.snapshot() if self.guard is not None else None)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -2149,6 +2246,11 @@ class Trainer:
                         b.copy_(v)
                     if self.flat_ema is not None:
                         self.flat_ema.copy_(snap[5])
+                    if self.guard is not None:
+                        if snap[7] is not None:
+                            self.guard.restore(snap[7])
+                        else:                           # (the table, and with it the guard, was built by the warm-up)
+                            self.guard.load_state(*(self._guard_resume or (snap[3], 0)))
                 self.iter, self.ema_steps = snap[3], snap[6]
         torch.cuda.current_stream(dev).wait_stream(side)
         self._refresh_dev()

@@ -7,6 +7,8 @@ existing launch and is kept for comparison) and 32 B per element for AdamW (p, g
 
     python tools/optim_step_bench.py [--out profiles/optim_step_bench.txt]
 
+--guard adds the step guard's launches (the finite pass, the verdict, ledn_optim_step_guarded) to the list.
+
 --trace sgd|adamw|adamw-clip runs nothing but --steps eager training steps (2 x 3 x 320 x 320, f32) for a kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/optim_step_bench.py --trace adamw): `steps` launches of optim_kernel
 where the plain configuration shows `steps` of sgd_kernel -- the step still ends in ONE optimizer launch, plus the norm
@@ -72,6 +74,8 @@ def main():
     p.add_argument('--repeats', type=int, default=30)
     p.add_argument('--trace', choices=['sgd', 'adamw', 'adamw-clip'], help='only run --steps eager steps (for a kernel trace)')
     p.add_argument('--steps', type=int, default=10)
+    p.add_argument('--guard', action='store_true',
+                   help='add the step guard: finite pass + verdict + ledn_optim_step_guarded next to ledn_optim_step, SGD and AdamW')
     p.add_argument('--out')
     a = p.parse_args()
     if a.trace:
@@ -108,6 +112,20 @@ def main():
              ('ledn_optim_step AdamW + paramwise      ', lambda: adamw.step(_lib.OPTIM_ADAMW, 0.0, t=10), 32),
              ('ledn_optim_step AdamW, scalars on device', lambda: adamw.step(_lib.OPTIM_ADAMW, 0.0, t=10, sched_dev=sched), 32),
              ('norm pass + ledn_optim_step AdamW (l2) ', adamw_clip, 36)]
+    if a.guard:
+        # the gradient stays finite (zeros): every guarded launch is an applied step, as every step of a healthy run is
+        guard = T.StepGuard(dev, adamw.n)
+
+        def guarded(table, kind, **kw):
+            def run():
+                guard.finite_pass(table)
+                guard.verdict(table, (0.9, 0.999), 0)
+                table.step(kind, 0.0, guard=guard, **kw)
+            return run
+        cases += [('finite pass alone                      ', lambda: guard.finite_pass(adamw), 4),
+                  ('finite pass + verdict                  ', lambda: (guard.finite_pass(adamw), guard.verdict(adamw)), 4),
+                  ('guard + ledn_optim_step_guarded SGD    ', guarded(gsgd, _lib.OPTIM_SGD, momentum=0.9), 20),
+                  ('guard + ledn_optim_step_guarded AdamW  ', guarded(adamw, _lib.OPTIM_ADAMW), 36)]
     for rep in range(2):                           # twice, alternating: the spread of a repeat is on the page
         for name, fn, per in cases:
             lines.append(f'  launch #{rep}  {name} {fmt(timed(fn, a.warmup, a.repeats), per * n)}  ({per} B/element)')

@@ -5,7 +5,9 @@ OhemCrossEntropy x2, SyncBN when launched with --launcher pytorch (one process p
 every 50 iterations, checkpoints in mmengine layout (iter_N.pth).  custom_hooks=[dict(type='EMAHook', ...)] in the
 config (or --cfg-options custom_hooks="[{'type':'EMAHook','momentum':0.001}]") switches weight averaging on: the
 Trainer reads it, the checkpoints then hold the averaged weights in 'state_dict' and the training weights in
-'ema_state_dict', and --resume undoes that swap.  Datasets/augmentation are out of scope
+'ema_state_dict', and --resume undoes that swap.  --cfg-options optim_wrapper.type=AmpOptimWrapper switches the step guard on: a step whose gradient holds an
+Inf or a NaN is left out on the device, the log line shows skipped_steps, and when the count has grown since the last log
+line one more line names the parameters of the last skipped step.  Datasets/augmentation are out of scope
 (SURVEY.md section 2): batches are synthetic Cityscapes-shaped uint8 images with a 16-px ignore border.
 
     python tools/train.py CONFIG [--work-dir DIR] [--max-iters N] [--batch-size B] [--resume]
@@ -30,7 +32,9 @@ def parse_args():
     p.add_argument('config')
     p.add_argument('--work-dir')
     p.add_argument('--resume', action='store_true', help='resume from the latest iter_*.pth in the work dir')
-    p.add_argument('--amp', action='store_true', help='bf16 activations (the default here; kept for CLI parity)')
+    p.add_argument('--amp', action='store_true',
+                   help='bf16 activations (the default here; kept for CLI parity).  The other half of the reference\'s --amp, '
+                        'leaving out steps with a non-finite gradient: --cfg-options optim_wrapper.type=AmpOptimWrapper')
     p.add_argument('--cfg-options', nargs='+', default=[], help='key=value overrides (model.backbone.channels=32 ...)')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none')
     p.add_argument('--local_rank', '--local-rank', type=int, default=0)
@@ -164,6 +168,7 @@ def main():
         trainer.capture(img, samples, warmup=args.capture_warmup, restore=True)
     t0, tlog = time.perf_counter(), time.perf_counter()
     first = trainer.iter
+    seen_skips = None                       # step guard: skipped_steps at the last log line
     nxt = prefetch(first) if first < max_iters else None
     for it in range(first, max_iters):
         (img, samples), ev = nxt
@@ -177,6 +182,14 @@ def main():
             print(f'Iter(train) [{it + 1:6d}/{max_iters}]  lr: {trainer.lr():.4e}  time: {dt:.4f}  '
                   + '  '.join(f'{k}: {v:.4f}' for k, v in vals.items())
                   + f'  data: {int(img.sum(dtype=torch.int64))}', flush=True)     # fingerprint of this iteration's batch
+            if 'skipped_steps' in vals:     # (optim_wrapper.type=AmpOptimWrapper; this line has synchronised already)
+                if seen_skips is not None and vals['skipped_steps'] > seen_skips or (seen_skips is None and vals['skipped_steps'] > 0):
+                    rep = trainer.nonfinite_report()
+                    if rep is not None:
+                        print(f'  non-finite gradient: last skipped step at iter {rep["iter"] + 1}, in '
+                              f'{", ".join(rep["params"][:8])}' + (f' (+{len(rep["params"]) - 8} more)' if len(rep["params"]) > 8
+                                                                  else ''), flush=True)
+                seen_skips = vals['skipped_steps']
         if rank == 0 and args.save_interval and (it + 1) % args.save_interval == 0 and it + 1 < max_iters:
             save(it + 1)
     torch.cuda.synchronize(dev)
